@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- candidates/s of the hashcat -a 5 table expansion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--words N]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--words N] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 One "step" = one full pass of the hot path over one batch already resident in HBM:
@@ -17,8 +17,12 @@ collective; the other collectives are the barrier and the max/sum timing reducti
 
 Prints ONE JSON line (rank 0) with the driver's fields plus "roofline" (expansion
 kernel: algorithmic bytes = sum(len(cand)+1) per launch / average launch time from
-HIP events on the library stream) and "cpu_baseline" (oracle/a5_oracle.c run with
-the reference's goroutine/channel/writer structure on a bounded sample).
+HIP events on the library stream).  A plain run sets up, warms up, times the steps and
+prints that line; ``--full`` adds the legs that take runs of their own: "cpu_baseline"
+(oracle/a5_oracle.c run with the reference's goroutine/channel/writer structure on a
+bounded sample) and "steady_state" (a stream of batches through two contexts).
+``--dump-outputs DIR`` writes what the last timed step left for its caller as
+DIR/<name>.npy (dump_expansion / dump_hits).
 """
 from __future__ import annotations
 
@@ -57,7 +61,10 @@ def parse():
     ap.add_argument("--max", type=int, default=15)
     ap.add_argument("--mode", type=int, default=0, choices=(0, 1, 2, 3),
                     help="0 processWord (headline), 1 -r, 2 -s, 3 -s -r (main.go:80-92)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the CPU baseline (unless "
+                         "--no-cpu-baseline) and the steady-state stream of --steady-batches batches")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-sample-words", type=int, default=120_000)
     ap.add_argument("--verify", action="store_true", help="digest-check the last step against the C oracle")
     ap.add_argument("--digest", default="none", choices=("none", "md5", "ntlm"),
@@ -69,14 +76,17 @@ def parse():
     ap.add_argument("--same-device", action="store_true",
                     help="every rank on device 0 (multi-rank tests on a one-GPU box)")
     ap.add_argument("--steady-batches", type=int, default=4,
-                    help="also time this many batches through two contexts on two host threads (batch k+1's "
-                         "keyspace under batch k's expansion): the steady-state line; 0 = off")
+                    help="with --full: also time this many batches through two contexts on two host threads "
+                         "(batch k+1's keyspace under batch k's expansion): the steady-state line; 0 = off")
     ap.add_argument("--stdout", action="store_true",
                     help="the reference's own output path (main.go:58-68): the CLI replica's stdout to /dev/null "
                          "and to a pipe, and a5x_expand into a host sink (PCIe-inclusive rates, never `value` of "
                          "the headline line)")
     ap.add_argument("--dump", default=None,
                     help="directory: per-rank per-word digests (expansion) / gathered hits (--digest) for tests")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="directory: what the last timed step computed, as DIR/<name>.npy (float32 / float64, "
+                         "<= 64 MB; seeded samples of the larger arrays), for comparing two builds")
     return ap.parse_args()
 
 
@@ -221,6 +231,63 @@ def latest_profile_traffic(workload: str, words: int, mode: int = 0):
                 and d.get("mode", 0) == mode and d.get("bytes_per_launch")):
             return d
     return None
+
+
+DUMP_SEED = 0xD0C5  # sample positions of --dump-outputs: the same in every run of the same arguments
+
+
+def _dump_save(args, D, name, arr):
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, name + (f"_rank{D.rank}" if D.world > 1 else "") + ".npy"), arr)
+
+
+def _u64_halves(a) -> np.ndarray:
+    """(n, k) u64 -> (n, 2k) float64: the low and the high 32 bits of every value (exact in float64)."""
+    a = np.ascontiguousarray(a, dtype="<u8")
+    return a.view("<u4").astype(np.float64).reshape(a.shape[0], 2 * a.shape[1])
+
+
+def _sample(rng, n: int, k: int) -> np.ndarray:
+    """Every index below n, or k of them (seeded, ascending)."""
+    return np.arange(n, dtype=np.int64) if n <= k else np.sort(rng.choice(n, size=k, replace=False))
+
+
+def dump_expansion(args, D, out, tc, tb, byte_off, digests):
+    """--dump-outputs of the expansion: what a5x_expand_device left for its caller in the last
+    timed step, <= 64 MB in all, every position drawn from DUMP_SEED:
+      totals.npy      f64 (3,)    candidates, output bytes, words of this rank's step
+      byte_off.npy    f64 (k, 2)  (word, d_byte_off[word]) of <= 500k words, the last entry included
+      candidates.npy  f32 (m,)    the "cand\\n" stream: all of it up to 8 MiB, else 2048 chunks of 4 KiB
+      chunk_off.npy   f64 (c,)    the byte offset of every chunk of candidates.npy
+      word_digest.npy f64 (j, 9)  word, then the 32-bit halves of a5x_digest_device's {candidates,
+                                  bytes, sum h, sum h^2} over ALL output bytes of <= 250k words"""
+    rng = np.random.default_rng(DUMP_SEED)
+    n = len(byte_off) - 1
+    _dump_save(args, D, "totals", np.array([tc, tb, n], dtype=np.float64))
+    w = _sample(rng, n, 500_000)
+    wi = np.append(w, n)
+    _dump_save(args, D, "byte_off", np.stack([wi, byte_off[wi]], axis=1).astype(np.float64))
+    chunk = 4096
+    if tb <= 2048 * chunk:
+        starts, parts = np.zeros(1, dtype=np.int64), [out.to_array(np.uint8, count=tb)]
+    else:
+        starts = _sample(rng, tb // chunk, 2048) * chunk
+        parts = [out.to_array(np.uint8, count=chunk, offset=int(s)) for s in starts]
+    _dump_save(args, D, "candidates", np.concatenate(parts).astype(np.float32))
+    _dump_save(args, D, "chunk_off", starts.astype(np.float64))
+    wd = w[:: max(1, -(-len(w) // 250_000))]
+    _dump_save(args, D, "word_digest", np.concatenate([wd[:, None].astype(np.float64), _u64_halves(digests[wd])], axis=1))
+
+
+def dump_hits(args, D, tc, rows):
+    """--dump-outputs of the fused digest: the hit records the last timed step returned, sorted
+    (the device appends them in no fixed order), the first 500k at most:
+      totals.npy  f64 (2,)    candidates digested, hits
+      hits.npy    f64 (h, 8)  32-bit halves of {global word, candidate in word, digest lo, digest hi}"""
+    rows = np.asarray(rows, dtype=np.uint64).reshape(-1, 4)
+    rows = rows[np.lexsort((rows[:, 3], rows[:, 2], rows[:, 1], rows[:, 0]))][:500_000]
+    _dump_save(args, D, "totals", np.array([tc, len(rows)], dtype=np.float64))
+    _dump_save(args, D, "hits", _u64_halves(rows))
 
 
 def cpu_model() -> str:
@@ -488,6 +555,8 @@ def run_digest(args, D):
     D.barrier()
     dt = time.perf_counter() - t0
     hits, st = res[-1]
+    if args.dump_outputs:  # every rank: the hits of its shard, global word indices
+        dump_hits(args, D, tc, hd.hits_to_rows(hits, word_base=w0))
     gathered = hd.gather_rows_u64(D.dist, hd.hits_to_rows(hits, word_base=w0), D.backend)  # rank 0: all ranks' hits
     dt_max = D.reduce(dt, "max")
     cands_all = D.reduce(float(tc) * args.steps, "sum")
@@ -521,7 +590,7 @@ def run_digest(args, D):
                                       "digests all-gathered); hit counts all-reduced, hit records gathered on rank 0 "
                                       "with global word indices"},
             "roofline": digest_roofline(args, tc, ms_dig, ms_exp, ms_ks, dt_max / args.steps * 1e3),
-            "cpu_baseline": None if args.no_cpu_baseline else digest_cpu_baseline(tables, args, targets),
+            "cpu_baseline": digest_cpu_baseline(tables, args, targets) if args.full and not args.no_cpu_baseline else None,
         }
         print(json.dumps(res_line), flush=True)
     D.barrier()
@@ -800,7 +869,7 @@ def main():
     launches = stats[-1]["expand_launches"]
     ms_exp_max = D.reduce(ms_exp, "max")
 
-    if args.verify or args.dump:
+    if args.verify or args.dump or args.dump_outputs:
         # per-word digests of this rank's bytes [rb, re_) of the local stream (a cut word:
         # the part this rank wrote; digests are sums, so the parts add up across ranks)
         bo_h = boff.to_array(np.uint64, count=n + 1)
@@ -812,6 +881,8 @@ def main():
         if args.dump:  # this rank's shard: per-word digests of words [w0, w1) of the global list
             os.makedirs(args.dump, exist_ok=True)
             np.save(os.path.join(args.dump, f"digest_{w0}_{w1}.npy"), got)
+        if args.dump_outputs:
+            dump_expansion(args, D, out, tc, tb, bo_h, got)
     if args.verify and (cb, ce) != (0, tc_all):
         raise SystemExit("--verify checks whole batches (one rank); the multi-rank check is tests/test_gpu_dist.py")
     if args.verify:
@@ -824,7 +895,7 @@ def main():
             raise SystemExit(f"verification failed on {bad} words")
 
     out.free()
-    steady = steady_state(args, D, tables, tb, n) if args.steady_batches > 0 and args.mode == 0 else None
+    steady = steady_state(args, D, tables, tb, n) if args.full and args.steady_batches > 0 and args.mode == 0 else None
 
     if D.rank == 0:
         achieved = tb / (ms_exp * 1e-3) / 1e9  # GB/s, algorithmic bytes per launch / launch time
@@ -879,7 +950,7 @@ def main():
             "cpu_baseline": None,
             "steady_state": steady,
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(tables, args)
         print(json.dumps(res), flush=True)
     D.barrier()

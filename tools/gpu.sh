@@ -181,7 +181,7 @@ step_stamps() {
 
 step_final() {  # part 1: tests, the headline C3 line and its evidence, C4, C2a, steady state
   TT=900 step_test || return $?
-  NAME=_c3 BENCH_ARGS="" step_bench || return $?
+  NAME=_c3 BENCH_ARGS="--full" step_bench || return $?
   BENCH_ARGS="--steady-batches 0" step_prof || return $?
   WL=c3 step_traffic || return $?
   NAME=_c4 BENCH_ARGS="--steps 3 --warmup 1 --no-cpu-baseline --workload c4 --words 12500000 --steady-batches 0" step_bench || return $?
@@ -191,7 +191,7 @@ step_final() {  # part 1: tests, the headline C3 line and its evidence, C4, C2a,
 step_final2() {  # part 2: fused digests (+ op breakdown), the -r / -s / -s -r lines and profiles, stdout path
   ALGOS="md5 ntlm" step_digestprof || return $?
   for alg in md5 ntlm; do
-    NAME=_digest_$alg BENCH_ARGS="--digest $alg --workload c5 --words 2000000 --targets 1000000 --steps 3 --warmup 1" \
+    NAME=_digest_$alg BENCH_ARGS="--full --digest $alg --workload c5 --words 2000000 --targets 1000000 --steps 3 --warmup 1" \
       step_bench || return $?
   done
   step_dabl || return $?
