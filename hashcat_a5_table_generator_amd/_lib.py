@@ -29,7 +29,7 @@ EXPORTS = (
     "a5x_digest_device", "a5x_partition", "a5x_dev_alloc", "a5x_dev_free", "a5x_memcpy_h2d",
     "a5x_memcpy_d2h", "a5x_synchronize", "a5x_debug_stamps", "a5x_debug_plan_word",
     "a5x_set_targets", "a5x_expand_digest", "a5x_expand_digest_device", "a5x_expand_digest_range_device",
-    "a5x_digest_lines_device",
+    "a5x_digest_lines_device", "a5x_digest_size", "a5x_hit_digest", "a5x_debug_digest",
     "a5x_format_plain", "a5x_format_hits", "a5x_locate_device", "a5x_split_device",
     "a5x_stream_reserve",
 )
@@ -53,7 +53,7 @@ class Stats(ctypes.Structure):
 
 
 class Hit(ctypes.Structure):
-    """a5x_hit: word index, candidate index inside the word, digest."""
+    """a5x_hit: word index, candidate index inside the word, digest (its first 16 bytes)."""
     _fields_ = [("word", ctypes.c_uint64), ("cand", ctypes.c_uint64), ("digest", ctypes.c_uint8 * 16)]
 
 
@@ -115,6 +115,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     L.a5x_expand_digest_range_device.argtypes = [vp, vp, vp, u64, i, i, i, u64, u64, u64, vp, u64, ctypes.POINTER(u64),
                                                  ctypes.POINTER(Stats), vp]
     L.a5x_digest_lines_device.argtypes = [vp, i, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
+    L.a5x_digest_size.argtypes = [i]
+    L.a5x_hit_digest.argtypes = [vp, ctypes.POINTER(Hit), vp, sz, ctypes.POINTER(sz)]
+    L.a5x_debug_digest.argtypes = [i, ctypes.c_char_p, sz, vp, sz]
     L.a5x_format_plain.argtypes = [ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz)]
     L.a5x_format_hits.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, SINK, vp]
     L.a5x_locate_device.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, vp]

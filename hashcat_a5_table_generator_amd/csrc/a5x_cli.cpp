@@ -6,11 +6,11 @@
 //
 //   a5x_generator <dict-file> -t <table> [-t <table> ...] [-m N] [-x N]
 //                 [--threads N] [-s] [-r] [--device N]
-//                 [--hashes <file> [--algo md5|ntlm]]
+//                 [--hashes <file> [--algo md5|ntlm|sha1|sha256]]
 //                 [--skip N] [--limit N] [--keyspace]
 //
 // --hashes (a5x extension): instead of printing the candidates for a
-// hashcat pipe (README.MD:69), hash them on the GPU (fused MD5 / NTLM + lookup) against
+// hashcat pipe (README.MD:69), hash them on the GPU (MD5 / NTLM / SHA-1 / SHA-256 + lookup) against
 // the hex digests of <file> and print what hashcat would report, "hash:plain" (plains
 // that hashcat would hexify as $HEX[...]), each target once, at its first candidate in
 // stream order (README.MD:74-106, :168).
@@ -56,7 +56,8 @@ static void usage(FILE* f) {
           "  -r, --reverse-sub                 Reverse substitution direction\n"
           "      --device=0                    GPU ordinal (a5x extension)\n"
           "      --hashes=FILE                 Crack: print hash:plain for the digests in FILE (a5x extension)\n"
-          "      --algo=md5                    Digest of --hashes: md5 (hashcat -m 0) or ntlm (-m 1000)\n"
+          "      --algo=md5                    Digest of --hashes: md5 (hashcat -m 0), ntlm (-m 1000),\n"
+          "                                    sha1 (-m 100) or sha256 (-m 1400)\n"
           "      --skip=0                      Resume: start at candidate N of the stream (a5x extension)\n"
           "      --limit=N                     Print at most N candidates (a5x extension)\n"
           "      --keyspace                    Print the number of candidates and exit (a5x extension)\n");
@@ -173,7 +174,8 @@ static int hexv(int c) {
   return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
 }
 
-// target digests: one hex digest per line (32 hex digits; anything after them, e.g. a
+// target digests: one hex digest per line (2 * a5x_digest_size(algo) hex digits: 32, 40
+// or 64; anything after them, e.g. a
 // ":plain" of a potfile line, is ignored); other lines are counted and skipped.  Whole
 // lines of any length (getline): a long potfile plain is one line, never a continuation
 // piece read as a target.
@@ -185,23 +187,26 @@ static int load_targets(a5x_ctx* ctx, const char* path, int algo) {
   size_t cap = 0;
   ssize_t n;
   uint64_t bad = 0;
+  const int dsz = a5x_digest_size(algo);
+  if (dsz <= 0 || dsz > 32) { fclose(f); return a5x_set_targets(ctx, algo, nullptr, 0); }  // (reports the bad algorithm)
+  const size_t nhex = 2 * (size_t)dsz;
   while ((n = getline(&line, &cap, f)) >= 0) {
     size_t k = 0;
-    uint8_t d[16];
-    for (; k < 32 && k < (size_t)n; k++) {
+    uint8_t d[32];
+    for (; k < nhex && k < (size_t)n; k++) {
       const int v = hexv((unsigned char)line[k]);
       if (v < 0) break;
       if (k & 1) d[k / 2] |= (uint8_t)v; else d[k / 2] = (uint8_t)(v << 4);
     }
-    const char t = (size_t)n > 32 ? line[32] : 0;
-    if (k == 32 && (t == 0 || t == '\n' || t == '\r' || t == ':')) dig.insert(dig.end(), d, d + 16);
+    const char t = (size_t)n > nhex ? line[nhex] : 0;
+    if (k == nhex && (t == 0 || t == '\n' || t == '\r' || t == ':')) dig.insert(dig.end(), d, d + dsz);
     else if (n > 0 && line[0] != '\n' && line[0] != '\r') bad++;
   }
   free(line);
   fclose(f);
-  if (bad) fprintf(stderr, "a5_generator: %llu line(s) of %s are not 32-hex-digit hashes (skipped)\n",
-                   (unsigned long long)bad, path);
-  return a5x_set_targets(ctx, algo, dig.empty() ? nullptr : dig.data(), dig.size() / 16);
+  if (bad) fprintf(stderr, "a5_generator: %llu line(s) of %s are not %zu-hex-digit hashes (skipped)\n",
+                   (unsigned long long)bad, path, nhex);
+  return a5x_set_targets(ctx, algo, dig.empty() ? nullptr : dig.data(), dig.size() / (size_t)dsz);
 }
 
 static bool parse_u64(const char* s, uint64_t* out) {
@@ -332,7 +337,9 @@ int main(int argc, char** argv) {
       std::string v = val_of("--algo");
       if (v == "md5" || v == "0") algo = A5X_ALGO_MD5;
       else if (v == "ntlm" || v == "1000") algo = A5X_ALGO_NTLM;
-      else { fprintf(stderr, "a5_generator: error: --algo: md5 or ntlm\n"); return 80; }
+      else if (v == "sha1" || v == "100") algo = A5X_ALGO_SHA1;
+      else if (v == "sha256" || v == "1400") algo = A5X_ALGO_SHA256;
+      else { fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1 or sha256\n"); return 80; }
     } else if (s.rfind("--skip", 0) == 0) {
       if (!parse_u64(val_of("--skip"), &skip)) { fprintf(stderr, "a5_generator: error: --skip: bad count\n"); return 80; }
       cursor = true;
@@ -527,8 +534,13 @@ int main(int argc, char** argv) {
       return x.word != y.word ? x.word < y.word : x.cand < y.cand;
     });
     std::vector<a5x_hit> first;
-    for (uint64_t h = 0; h < nh; h++)
-      if (cracked.insert(std::string((const char*)hits[h].digest, 16)).second) first.push_back(hits[h]);
+    for (uint64_t h = 0; h < nh && rc == 0; h++) {  // keyed on the full digest (20 / 32 bytes for SHA-1 / SHA-256)
+      uint8_t full[32];
+      size_t fl = 0;
+      if ((rc = a5x_hit_digest(ctx, &hits[h], full, sizeof full, &fl))) break;
+      if (cracked.insert(std::string((const char*)full, fl)).second) first.push_back(hits[h]);
+    }
+    if (rc) break;
     rc = a5x_format_hits(ctx, wb, sub.data(), nb, mode, tmin, tmax, first.data(), first.size(), sink_stdout,
                          nullptr);
   }

@@ -7,11 +7,13 @@
 //   MD5   RFC 1321 over the candidate bytes (== Go crypto/md5);
 //   NTLM  MD4 (RFC 1320) over UTF-16LE of the candidate decoded as Go does for
 //         []rune(string): invalid UTF-8 byte -> U+FFFD, runes > U+FFFF -> surrogate
-//         pairs (unicode/utf16.Encode).
+//         pairs (unicode/utf16.Encode);
+//   SHA-1 / SHA-256  FIPS 180-4 over the candidate bytes (a5x_sha.h).
 // Each digest is probed against a device-resident target set: a 2^k-bit prefilter
-// indexed by digest word 0, then an open-addressing table of 16-B digests.
+// indexed by digest word 0, then an open-addressing table of the first 16 digest bytes
+// (wide digests: the remaining words in a parallel array, compared too).
 //
-// Work unit: one wave per 2 KiB block of the stream.  The wave stages the block (+256 B
+// Work unit: one wave per 2 or 4 KiB block of the stream (DCfg).  The wave stages the block (+256 B
 // of the next one) in LDS, finds line starts with a SWAR newline test (exact per byte),
 // compacts them into an ordered start list, and every lane hashes one candidate at a
 // time; the candidate owned by a block is the one STARTING in it.  A hit records
@@ -24,6 +26,7 @@
 #include "a5x_format.h"
 #include "a5x_launch.h"
 #include "a5x_md.h"
+#include "a5x_sha.h"
 
 namespace {
 
@@ -31,8 +34,19 @@ typedef uint64_t u64;
 typedef uint32_t u32;
 
 // stream bytes per wave: 4 KiB for MD5 (lanes stay busy over ~3 rounds of candidates),
-// 2 KiB for NTLM (the MD4 of UTF-16LE costs about twice per candidate byte)
-template <bool MD5> struct DCfg { static constexpr u32 BLK = MD5 ? 4096u : 2048u; };
+// 2 KiB for NTLM (the MD4 of UTF-16LE costs about twice per candidate byte), 4 KiB for
+// SHA-1 / SHA-256: their time is the hash rounds, and a block's last round of 64 lanes is
+// only part full -- C5's ~23-byte lines give 2 rounds per 2 KiB block, the second 40 %
+// full, against 3 rounds (the third 80 % full) per 4 KiB block; measured on C5 the digest
+// pass takes 83.4 vs 97.3 ms (SHA-1) and 132.4 vs 161.7 ms (SHA-256) at 4 vs 2 KiB
+// (profiles/r07_ab_sha_stream_block.json); DW = 32-bit words of the digest
+#ifndef A5X_SHA_DBLK
+#define A5X_SHA_DBLK 4096u  // (A/B knob: 2048u or 4096u)
+#endif
+template <int ALGO> struct DCfg {
+  static constexpr u32 BLK = ALGO == A5X_ALGO_MD5 ? 4096u : (ALGO == A5X_ALGO_NTLM ? 2048u : A5X_SHA_DBLK);
+  static constexpr u32 DW = ALGO == A5X_ALGO_SHA1 ? 5u : (ALGO == A5X_ALGO_SHA256 ? 8u : 4u);
+};
 constexpr u32 DMARGIN = 256;               // next-block bytes staged for straddling lines
 constexpr u32 D_ERR_HITCAP = 1u << 10;     // more hits than the caller's buffer
 
@@ -93,6 +107,22 @@ __device__ __forceinline__ void md_digest(const uint8_t* lbase, u32 loff, const 
 __device__ __forceinline__ bool probe(const A5xDigLaunch& a, const u32* d) {
   return md_probe(a.bitmap, a.bm_mask, a.table, a.tmask, a.has_zero_target != 0, d);
 }
+template <int TW>
+__device__ __forceinline__ bool probe_wide(const A5xDigLaunch& a, const u32* d) {
+  return md_probe_wide<TW>(a.bitmap, a.bm_mask, a.table, a.tails, a.tmask, a.has_zero_target != 0, a.ztails,
+                           a.nztails, d);
+}
+
+// message bytes of a line for sha_digest: the staged LDS bytes, or HBM for a line that
+// runs past them (the switch md_digest makes per word)
+struct ShaLine {
+  const uint8_t* lbase;
+  u32 loff;
+  const uint8_t* gbase;
+  u64 goff, glim;
+  bool lds;
+  __device__ __forceinline__ u32 at4(u32 i) const { return lds ? lds4(lbase, loff + i) : glob4(gbase, goff + i, glim); }
+};
 
 template <u32 BLK>
 struct DWave {
@@ -102,13 +132,15 @@ struct DWave {
 };
 
 // op 0: probe targets, record hits; op 1: count line starts per block; op 2: write
-// every candidate's digest at dig_out[16 * (blk_pre[blk] + i)]
-template <bool MD5>
+// every candidate's digest at dig_out[4 * DW * (blk_pre[blk] + i)] (16, 20 or 32 bytes)
+template <int ALGO>
 __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
+  static_assert(DCfg<ALGO>::BLK == 2048u || DCfg<ALGO>::BLK == 4096u, "a5x_digest_lds sizes these two");
   extern __shared__ __attribute__((aligned(16))) uint8_t d_dyn[];
   const u32 wv = threadIdx.x / 64, lane = d_lane();
   const u32 nwv = blockDim.x / 64;
-  constexpr u32 DBLK = DCfg<MD5>::BLK;
+  constexpr u32 DBLK = DCfg<ALGO>::BLK;
+  constexpr u32 DW = DCfg<ALGO>::DW;
   typedef DWave<DBLK> WT;
   constexpr u32 DBUF = WT::BUF;
   constexpr u32 NM = DBLK / 2048u;  // 32-bit newline masks per lane (32 B each)
@@ -199,9 +231,15 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
       // every byte of the line staged (bytes past sl are zero-filled) and the 8-B
       // over-read of the last message word inside the buffer
       const bool in_lds = e <= sl && e + 8 <= DBUF;
-      u32 d[4];
-      if (MD5) {
+      u32 d[DW];
+      if constexpr (ALGO == A5X_ALGO_MD5) {
         md_digest<true>(W.data, s, a.out, bs + s, a.nbytes, in_lds, len, d);
+      } else if constexpr (DW > 4) {
+        ShaLine src;
+        src.lbase = W.data; src.loff = s;
+        src.gbase = a.out; src.goff = bs + s; src.glim = a.nbytes;
+        src.lds = in_lds;
+        sha_digest<ALGO>(src, len, d);
       } else if (in_lds) {  // any length: the UTF-16LE units are made as MD4 blocks fill
         MdLds src;
         src.base = W.data;
@@ -214,15 +252,31 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
         src.lim = a.nbytes;
         ntlm_stream(src, len, d);
       }
+      bool hit = false;
       if (op == 2) {
-        uint4* o4 = (uint4*)(a.dig_out + 16 * (a.blk_pre[blk] + i));
-        *o4 = make_uint4(d[0], d[1], d[2], d[3]);
-      } else if (probe(a, d)) {
+        if constexpr (DW == 4) {
+          uint4* o4 = (uint4*)(a.dig_out + 16 * (a.blk_pre[blk] + i));
+          *o4 = make_uint4(d[0], d[1], d[2], d[3]);
+        } else {  // a 20-B stride is only 4-B aligned: dword stores
+          u32* o1 = (u32*)(a.dig_out + 4ull * DW * (a.blk_pre[blk] + i));
+#pragma unroll
+          for (u32 k = 0; k < DW; k++) o1[k] = d[k];
+        }
+      } else if constexpr (DW == 4) {
+        hit = probe(a, d);
+      } else {
+        hit = probe_wide<(int)DW - 4>(a, d);
+      }
+      if (hit) {
         const u32 h = atomicAdd(a.nhits, 1u);
         if (h < a.hit_cap) {
           A5xHitRaw r;
           r.blk = blk; r.idx = i; r.d[0] = d[0]; r.d[1] = d[1]; r.d[2] = d[2]; r.d[3] = d[3];
           a.hits[h] = r;
+          if constexpr (DW > 4) {
+#pragma unroll
+            for (u32 k = 0; k < 4; k++) a.hit_tail[4ull * h + k] = k < DW - 4 ? d[4 + k] : 0u;
+          }
         } else {
           err |= D_ERR_HITCAP;
         }
@@ -295,26 +349,40 @@ hipError_t a5x_launch_gather_words(const uint8_t* words, const uint64_t* woff, c
   return hipGetLastError();
 }
 
+// the algorithm's stream block (0: not an algorithm)
+static u32 digest_blk(int algo) {
+  return algo == A5X_ALGO_MD5 ? DCfg<A5X_ALGO_MD5>::BLK : algo == A5X_ALGO_NTLM ? DCfg<A5X_ALGO_NTLM>::BLK
+       : algo == A5X_ALGO_SHA1 ? DCfg<A5X_ALGO_SHA1>::BLK : algo == A5X_ALGO_SHA256 ? DCfg<A5X_ALGO_SHA256>::BLK : 0u;
+}
 size_t a5x_digest_lds(int algo) {
-  const u32 per = algo == A5X_ALGO_MD5 ? (u32)sizeof(DWave<DCfg<true>::BLK>) : (u32)sizeof(DWave<DCfg<false>::BLK>);
+  const u32 blk = digest_blk(algo);
+  const u32 per = blk == 4096u ? (u32)sizeof(DWave<4096u>) : (u32)sizeof(DWave<2048u>);
   return 4u * ((per + 15u) & ~15u);
 }
 
 hipError_t a5x_launch_digest_stream(const A5xDigLaunch& L, int op, uint32_t grid, hipStream_t st) {
   if (L.nbytes == 0) return hipSuccess;
   if (((uintptr_t)L.out & 15u) != 0) return hipErrorInvalidValue;
+  // op 0 of a wide digest compares the slots' tails and records each hit's tail
+  if (op == 0 && L.algo >= A5X_ALGO_SHA1 && (!L.hit_tail || !L.tails)) return hipErrorInvalidValue;
   const u64 nblk = a5x_digest_blocks(L.nbytes, L.algo);
   const u64 want = (nblk + 3) / 4;
   const u32 g = (u32)(want < grid ? want : grid);
   if (L.algo == A5X_ALGO_MD5)
-    hipLaunchKernelGGL(k_digest_stream<true>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+    hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_MD5>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+  else if (L.algo == A5X_ALGO_NTLM)
+    hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_NTLM>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+  else if (L.algo == A5X_ALGO_SHA1)
+    hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA1>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+  else if (L.algo == A5X_ALGO_SHA256)
+    hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA256>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
   else
-    hipLaunchKernelGGL(k_digest_stream<false>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+    return hipErrorInvalidValue;  // a missing kernel is an error, never another algorithm's digest
   return hipGetLastError();
 }
 
 uint64_t a5x_digest_blocks(uint64_t nbytes, int algo) {
-  const u64 b = algo == A5X_ALGO_MD5 ? DCfg<true>::BLK : DCfg<false>::BLK;
+  const u64 b = digest_blk(algo) ? digest_blk(algo) : DCfg<A5X_ALGO_MD5>::BLK;
   return (nbytes + b - 1) / b;
 }
 

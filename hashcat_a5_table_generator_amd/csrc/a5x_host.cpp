@@ -17,6 +17,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <memory>
@@ -28,6 +30,7 @@
 #include "a5x_gosem.h"
 #include "a5x_launch.h"
 #include "a5x_md.h"
+#include "a5x_sha.h"
 
 namespace {
 
@@ -118,6 +121,16 @@ struct a5x_ctx {
   DevBuf<uint8_t> dg_scratch;
   DevBuf<uint64_t> dg_blk_cnt, dg_blk_pre, dg_cand_off, dg_byte_off;
   DevBuf<A5xHitRaw> dg_hits;
+  // wide algorithms (SHA-1 / SHA-256): t_tw tail words per digest past the first four --
+  // per table slot (t_tails), of the zero-prefix targets (t_ztails), per device hit
+  // (dg_hit_tail, 4 words each); the sorted unique digests on the host (a5x_hit_digest),
+  // whether two of them share their first 16 bytes, and for such prefixes the tails the
+  // latest expand_digest call's hits matched, keyed by (word, cand)
+  uint32_t t_tw = 0, t_nz = 0;
+  DevBuf<uint32_t> t_tails, t_ztails, dg_hit_tail;
+  std::vector<uint8_t> t_full;
+  bool t_shared_prefix = false;
+  std::map<std::pair<uint64_t, uint64_t>, std::array<uint32_t, 4>> t_hit_tails;
   hipEvent_t dev_ev[2] = {nullptr, nullptr};
 
   DevBuf<uint64_t> count, bytes, cand_off, byte_off, scan_tmp, locate;
@@ -1239,7 +1252,134 @@ A5xDigLaunch dig_launch(a5x_ctx* c) {
   D.bm_mask = c->t_bm_log2 >= 32 ? 0xffffffffu : (uint32_t)((1ull << c->t_bm_log2) - 1);
   D.table = c->t_table.p; D.tmask = c->t_tmask; D.has_zero_target = c->t_has_zero;
   D.err = c->d_scalars + 2;
+  if (c->t_tw) {
+    D.tails = c->t_tails.p; D.ztails = c->t_ztails.p; D.nztails = c->t_nz;
+  }
   return D;
+}
+
+// digest bytes per algorithm (a5x_digest_size), 0: not an algorithm
+inline uint32_t algo_size(int algo) {
+  return algo == A5X_ALGO_MD5 || algo == A5X_ALGO_NTLM ? 16u : algo == A5X_ALGO_SHA1 ? 20u : algo == A5X_ALGO_SHA256 ? 32u : 0u;
+}
+
+// the context's sorted unique wide digests, in place
+template <size_t W>
+void sort_unique_digests(std::vector<uint8_t>& v) {
+  struct E { uint8_t b[W]; };
+  E* p = (E*)v.data();
+  const size_t n = v.size() / W;
+  std::sort(p, p + n, [](const E& x, const E& y) { return memcmp(x.b, y.b, W) < 0; });
+  E* e = std::unique(p, p + n, [](const E& x, const E& y) { return memcmp(x.b, y.b, W) == 0; });
+  v.resize((size_t)(e - p) * W);
+}
+
+// The target set as a5x_set_targets uploads it, built on the host from n digests of W
+// bytes: the prefilter bitmap, the open-addressing table of the first 16 bytes, the tail
+// words per slot and of the zero-prefix targets (wide digests), and the sorted unique
+// digests a5x_hit_digest answers from.
+struct TargetSet {
+  uint32_t bm_log2 = 0, has_zero = 0;
+  uint64_t tmask = 0;
+  std::vector<uint32_t> bm, tails, ztails;
+  std::vector<uint4> tab;
+  std::vector<uint8_t> full;
+  bool shared = false;  // two digests share their first 16 bytes
+};
+void build_target_set(uint32_t W, const uint8_t* dig, uint64_t n, TargetSet& T) {
+  // prefilter: >= 64 bits per target (false-positive rate <= 1/64), table: load <= 1/2
+  uint32_t bm_log2 = 16;
+  const uint32_t TW = W / 4 - 4;  // tail words
+  while (bm_log2 < 32 && (1ull << bm_log2) < n * 64) bm_log2++;
+  // (test hook: force the prefilter size, e.g. the 2^32-bit filter of > 2^26 targets)
+  if (const char* e = getenv("A5X_TARGET_BM_LOG2")) bm_log2 = std::max(16u, std::min(32u, (uint32_t)atoi(e)));
+  uint64_t tsz = 16;
+  while (tsz < 2 * n) tsz <<= 1;
+  std::vector<uint32_t>& bm = T.bm;
+  std::vector<uint4>& tab = T.tab;
+  bm.assign((1ull << bm_log2) / 32, 0);
+  tab.resize(tsz);
+  memset(tab.data(), 0, tsz * sizeof(uint4));
+  // wide digests: the words past the first four, per slot; the zero-prefix targets' tails
+  std::vector<uint32_t>&tails = T.tails, &ztails = T.ztails;
+  tails.assign(TW ? tsz * TW : 0, 0);
+  ztails.clear();
+  uint32_t has_zero = 0;
+  const uint64_t tmask = tsz - 1;
+  for (uint64_t i = 0; i < n; i++) {
+    uint32_t d[8];
+    memcpy(d, dig + (uint64_t)W * i, W);
+    if ((d[0] | d[1] | d[2] | d[3]) == 0) {
+      has_zero = 1;
+      ztails.insert(ztails.end(), d + 4, d + 4 + TW);
+      continue;
+    }
+    const uint32_t bi = d[0] & (uint32_t)((1ull << bm_log2) - 1);
+    if (MD_BLOOM2) {  // (a5x_md.h md_prefilter: the 64-bit word of bi, two bits from word 3)
+      const uint64_t m = md_bloom_bits(d[3]);
+      bm[(bi >> 6) * 2] |= (uint32_t)m;
+      bm[(bi >> 6) * 2 + 1] |= (uint32_t)(m >> 32);
+    } else {
+      bm[bi >> 5] |= 1u << (bi & 31);
+    }
+    for (uint64_t slot = tgt_slot(d, tmask);; slot = (slot + 1) & tmask) {
+      uint4& e = tab[slot];
+      if (e.x == d[0] && e.y == d[1] && e.z == d[2] && e.w == d[3] &&
+          (!TW || memcmp(&tails[slot * TW], d + 4, 4 * TW) == 0))
+        break;  // duplicate (an equal prefix with another tail takes a slot of its own)
+      if ((e.x | e.y | e.z | e.w) == 0) {
+        e = make_uint4(d[0], d[1], d[2], d[3]);
+        if (TW) memcpy(&tails[slot * TW], d + 4, 4 * TW);
+        break;
+      }
+    }
+  }
+  // the host copy a5x_hit_digest answers from (wide algorithms only)
+  std::vector<uint8_t>& full = T.full;
+  full.clear();
+  bool shared = false;
+  if (TW) {
+    full.assign(dig, dig + (uint64_t)W * n);
+    if (W == 20) sort_unique_digests<20>(full); else sort_unique_digests<32>(full);
+    for (size_t i = 1; i < full.size() / W && !shared; i++)
+      shared = memcmp(&full[(i - 1) * W], &full[i * W], 16) == 0;
+  }
+  T.bm_log2 = bm_log2;
+  T.has_zero = has_zero;
+  T.tmask = tmask;
+  T.shared = shared;
+}
+
+// The full digest of a hit (a5x_hit_digest): narrow algorithms, the hit's own bytes; wide
+// ones, the target with the hit's first 16 bytes -- and where several targets share them,
+// the one whose tail the latest expand_digest call recorded for the hit's (word, cand).
+int hit_full_digest(a5x_ctx* c, const a5x_hit* h, uint8_t* out) {
+  const uint32_t W = algo_size(c->t_algo);
+  if (W == 16) {
+    memcpy(out, h->digest, 16);
+    return A5X_OK;
+  }
+  const size_t n = c->t_full.size() / W;
+  const uint8_t* base = c->t_full.data();
+  size_t lo = 0, hi = n;  // first digest with prefix >= the hit's
+  while (lo < hi) {
+    const size_t mid = lo + (hi - lo) / 2;
+    if (memcmp(base + mid * W, h->digest, 16) < 0) lo = mid + 1; else hi = mid;
+  }
+  size_t e = lo;
+  while (e < n && memcmp(base + e * W, h->digest, 16) == 0) e++;
+  if (e == lo) return fail(c, A5X_E_ARG, "no target with the hit's first 16 digest bytes");
+  if (e - lo > 1) {
+    const auto it = c->t_hit_tails.find(std::make_pair(h->word, h->cand));
+    if (it == c->t_hit_tails.end())
+      return fail(c, A5X_E_ARG, "%zu targets share the hit's first 16 digest bytes and the hit is not one of the latest call's",
+                  e - lo);
+    for (; lo < e; lo++)
+      if (memcmp(base + lo * W + 16, it->second.data(), W - 16) == 0) break;
+    if (lo == e) return fail(c, A5X_E_ARG, "no target with the hit's digest");
+  }
+  memcpy(out, base + lo * W, W);
+  return A5X_OK;
 }
 
 uint32_t dig_grid(a5x_ctx* c) { return (uint32_t)std::max(1, c->cus) * 8u; }
@@ -1296,6 +1436,12 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
                   uint64_t rb, uint64_t re, uint64_t scratch_bytes, a5x_hit* hits, uint64_t hit_cap,
                   uint64_t* n_hits, a5x_stats* stats, hipStream_t st, bool allow_fused, uint64_t trim = 0) {
   int rc;
+  // SHA-1 / SHA-256: the two-pass range loop in every mode (no fused kernel hashes them)
+  const bool wide = c->t_tw != 0;
+  if (wide) {
+    allow_fused = false;
+    c->t_hit_tails.clear();
+  }
   Job J;
   job_open(c, J, d_words, d_woff, nw, mode, mn, mx, st);
   J.lengths = mode == A5X_MODE_DEFAULT || !allow_fused;  // the fused -r / -s digest needs no layout
@@ -1493,6 +1639,8 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   if ((rc = grow(c, c->dg_scratch, cap + 64))) return rc;
   uint64_t dev_hits = std::max<uint64_t>(1024, std::min<uint64_t>(hit_cap, 1u << 20));
   if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
+  if (wide && (rc = grow(c, c->dg_hit_tail, 4 * dev_hits))) return rc;
+  std::vector<uint32_t> htail;  // wide: the range's hit tails
   a5x_stats total;
   memset(&total, 0, sizeof total);
   total.words = nw;
@@ -1524,6 +1672,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
     }
     for (;;) {  // a range with more hits than the device buffer is digested again with room for all
       D.hits = c->dg_hits.p;
+      D.hit_tail = wide ? c->dg_hit_tail.p : nullptr;
       D.hit_cap = (uint32_t)dev_hits;
       D.nhits = c->d_scalars + 8;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 8, 0, 4, J.st));
@@ -1541,6 +1690,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       if (nh <= dev_hits || copied >= hit_cap) break;
       dev_hits = nh;  // grow and run this range's digest again (its candidates are still in scratch)
       if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
+      if (wide && (rc = grow(c, c->dg_hit_tail, 4 * dev_hits))) return rc;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 2, 0, 4, J.st));
     }
     if (nh) {
@@ -1552,7 +1702,15 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       const uint64_t take = std::min(hit_cap - std::min(hit_cap, copied), got);
       if (take)
         HIPCHK(c, hipMemcpyAsync(hits + copied, c->dg_hits.p, take * sizeof(a5x_hit), hipMemcpyDeviceToHost, J.st));
+      if (take && c->t_shared_prefix) {
+        htail.resize(4 * take);
+        HIPCHK(c, hipMemcpyAsync(htail.data(), c->dg_hit_tail.p, take * 16, hipMemcpyDeviceToHost, J.st));
+      }
       HIPCHK(c, hipStreamSynchronize(J.st));
+      if (take && c->t_shared_prefix)  // (which of the targets sharing a prefix each hit matched: a5x_hit_digest)
+        for (uint64_t k = 0; k < take; k++)
+          c->t_hit_tails[std::make_pair(hits[copied + k].word, hits[copied + k].cand)] = {
+              htail[4 * k], htail[4 * k + 1], htail[4 * k + 2], htail[4 * k + 3]};
       copied += take;
       found += nh;
     }
@@ -1666,6 +1824,7 @@ void a5x_destroy(a5x_ctx* c) {
   release(c->m_item_w);
   release(c->t_bitmap); release(c->t_table); release(c->dg_scratch); release(c->dg_blk_cnt); release(c->dg_blk_pre);
   release(c->dg_cand_off); release(c->dg_byte_off); release(c->dg_hits);
+  release(c->t_tails); release(c->t_ztails); release(c->dg_hit_tail);
   release(c->hy_list); release(c->hy_lens); release(c->hy_off); release(c->hy_words);
   for (auto& e : c->dev_ev)
     if (e) (void)hipEventDestroy(e);
@@ -2224,47 +2383,30 @@ int a5x_debug_plan_word(a5x_ctx* c, const uint8_t* word, size_t len, int mn, int
 int a5x_set_targets(a5x_ctx* c, int algo, const uint8_t* dig, uint64_t n) {
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || (n && !dig)) return A5X_E_ARG;
-  if (algo != A5X_ALGO_MD5 && algo != A5X_ALGO_NTLM) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
+  const uint32_t W = algo_size(algo);  // digest bytes
+  if (!W) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
+  const uint32_t TW = W / 4 - 4;       // tail words
   HIPCHK(c, hipSetDevice(c->device));
-  // prefilter: >= 64 bits per target (false-positive rate <= 1/64), table: load <= 1/2
-  uint32_t bm_log2 = 16;
-  while (bm_log2 < 32 && (1ull << bm_log2) < n * 64) bm_log2++;
-  // (test hook: force the prefilter size, e.g. the 2^32-bit filter of > 2^26 targets)
-  if (const char* e = getenv("A5X_TARGET_BM_LOG2")) bm_log2 = std::max(16u, std::min(32u, (uint32_t)atoi(e)));
-  uint64_t tsz = 16;
-  while (tsz < 2 * n) tsz <<= 1;
-  std::vector<uint32_t> bm((1ull << bm_log2) / 32, 0);
-  std::vector<uint4> tab(tsz);
-  memset(tab.data(), 0, tsz * sizeof(uint4));
-  uint32_t has_zero = 0;
-  const uint64_t tmask = tsz - 1;
-  for (uint64_t i = 0; i < n; i++) {
-    uint32_t d[4];
-    memcpy(d, dig + 16 * i, 16);
-    if ((d[0] | d[1] | d[2] | d[3]) == 0) { has_zero = 1; continue; }
-    const uint32_t bi = d[0] & (uint32_t)((1ull << bm_log2) - 1);
-    if (MD_BLOOM2) {  // (a5x_md.h md_prefilter: the 64-bit word of bi, two bits from word 3)
-      const uint64_t m = md_bloom_bits(d[3]);
-      bm[(bi >> 6) * 2] |= (uint32_t)m;
-      bm[(bi >> 6) * 2 + 1] |= (uint32_t)(m >> 32);
-    } else {
-      bm[bi >> 5] |= 1u << (bi & 31);
-    }
-    for (uint64_t slot = tgt_slot(d, tmask);; slot = (slot + 1) & tmask) {
-      uint4& e = tab[slot];
-      if (e.x == d[0] && e.y == d[1] && e.z == d[2] && e.w == d[3]) break;  // duplicate
-      if ((e.x | e.y | e.z | e.w) == 0) { e = make_uint4(d[0], d[1], d[2], d[3]); break; }
-    }
-  }
+  TargetSet T;
+  build_target_set(W, dig, n, T);
   int rc;
-  if ((rc = grow(c, c->t_bitmap, bm.size())) || (rc = grow(c, c->t_table, tsz))) return rc;
-  HIPCHK(c, hipMemcpy(c->t_bitmap.p, bm.data(), bm.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->t_table.p, tab.data(), tsz * sizeof(uint4), hipMemcpyHostToDevice));
+  if ((rc = grow(c, c->t_bitmap, T.bm.size())) || (rc = grow(c, c->t_table, T.tab.size()))) return rc;
+  if (TW && ((rc = grow(c, c->t_tails, T.tails.size())) || (rc = grow(c, c->t_ztails, T.ztails.size() + 1)))) return rc;
+  HIPCHK(c, hipMemcpy(c->t_bitmap.p, T.bm.data(), T.bm.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->t_table.p, T.tab.data(), T.tab.size() * sizeof(uint4), hipMemcpyHostToDevice));
+  if (TW) HIPCHK(c, hipMemcpy(c->t_tails.p, T.tails.data(), T.tails.size() * 4, hipMemcpyHostToDevice));
+  if (!T.ztails.empty())
+    HIPCHK(c, hipMemcpy(c->t_ztails.p, T.ztails.data(), T.ztails.size() * 4, hipMemcpyHostToDevice));
+  c->t_tw = TW;
+  c->t_nz = TW ? (uint32_t)(T.ztails.size() / TW) : 0;
+  c->t_full.swap(T.full);
+  c->t_shared_prefix = T.shared;
+  c->t_hit_tails.clear();
   c->t_algo = algo;
   c->n_targets = n;
-  c->t_bm_log2 = bm_log2;
-  c->t_tmask = tmask;
-  c->t_has_zero = has_zero;
+  c->t_bm_log2 = T.bm_log2;
+  c->t_tmask = T.tmask;
+  c->t_has_zero = T.has_zero;
   return A5X_OK;
 }
 
@@ -2314,8 +2456,9 @@ int a5x_digest_lines_device(a5x_ctx* c, int algo, const uint8_t* d_lines, uint64
                             uint64_t cap, uint64_t* n_lines, void* stream) {
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || (nbytes && !d_lines)) return A5X_E_ARG;
-  if (algo != A5X_ALGO_MD5 && algo != A5X_ALGO_NTLM) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
+  if (!algo_size(algo)) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
   if (((uintptr_t)d_lines & 15u) != 0) return fail(c, A5X_E_ARG, "d_lines must be 16-byte aligned");
+  if (algo_size(algo) > 16 && ((uintptr_t)d_dig & 3u) != 0) return fail(c, A5X_E_ARG, "d_digests must be 4-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   if (n_lines) *n_lines = 0;
@@ -2337,6 +2480,39 @@ int a5x_digest_lines_device(a5x_ctx* c, int algo, const uint8_t* d_lines, uint64
   HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   return decode_dev_err(c, c->h_scalars[2]);
+}
+
+int a5x_digest_size(int algo) {
+  const uint32_t w = algo_size(algo);
+  return w ? (int)w : A5X_E_ARG;
+}
+
+int a5x_hit_digest(a5x_ctx* c, const a5x_hit* hit, uint8_t* out, size_t cap, size_t* out_len) {
+  if (!c || !hit || !out_len) return A5X_E_ARG;
+  if (c->t_algo < 0) return fail(c, A5X_E_ARG, "no target set (a5x_set_targets)");
+  const uint32_t W = algo_size(c->t_algo);
+  *out_len = W;
+  if (!out) return A5X_OK;
+  if (cap < W) return fail(c, A5X_E_CAPACITY, "digest of %u bytes, buffer has %zu", W, cap);
+  uint8_t d[32];
+  const int rc = hit_full_digest(c, hit, d);
+  if (rc) return rc;
+  memcpy(out, d, W);
+  return A5X_OK;
+}
+
+int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, size_t cap) {
+  if ((algo != A5X_ALGO_SHA1 && algo != A5X_ALGO_SHA256) || (!msg && len) || !out || len > 0xffffff00u) return A5X_E_ARG;
+  const uint32_t W = algo_size(algo);
+  if (cap < W) return A5X_E_CAPACITY;
+  ShaBytes src;
+  src.p = msg;
+  src.n = (uint32_t)len;
+  uint32_t d[8];
+  if (algo == A5X_ALGO_SHA1) sha_digest<A5X_ALGO_SHA1>(src, (uint32_t)len, d);
+  else sha_digest<A5X_ALGO_SHA256>(src, (uint32_t)len, d);
+  memcpy(out, d, W);
+  return A5X_OK;
 }
 
 int a5x_partition(const uint64_t* prefix, uint64_t n, uint32_t parts, uint64_t* split) {
@@ -2405,6 +2581,13 @@ int a5x_format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint
   if (!n_hits) return A5X_OK;
   int rc;
   if ((rc = check_mode(c, mode))) return rc;
+  // the digests to print: the hits' own 16 bytes, or the full-width digests of a wide target set
+  const uint32_t dsz = c->t_tw ? algo_size(c->t_algo) : 16u;
+  std::vector<uint8_t> full((size_t)dsz * n_hits);
+  for (uint64_t h = 0; h < n_hits; h++) {
+    if (!c->t_tw) memcpy(&full[(size_t)16 * h], hits[h].digest, 16);
+    else if ((rc = hit_full_digest(c, &hits[h], &full[(size_t)dsz * h]))) return rc;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   // The hit words, once each, as a sub-batch; only the hit candidates themselves are
   // regenerated on the device (located, then expanded as single-candidate ranges, or
@@ -2510,9 +2693,9 @@ int a5x_format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint
   std::string o;
   for (uint64_t h = 0; h < n_hits; h++) {
     const size_t k = (size_t)(std::lower_bound(ug.begin(), ug.end(), g[h]) - ug.begin());
-    for (int i = 0; i < 16; i++) {
-      o += hx[hits[h].digest[i] >> 4];
-      o += hx[hits[h].digest[i] & 15];
+    for (uint32_t i = 0; i < dsz; i++) {
+      o += hx[full[(size_t)dsz * h + i] >> 4];
+      o += hx[full[(size_t)dsz * h + i] & 15];
     }
     o += ':';
     append_plain(o, (const uint8_t*)plain[k].data(), plain[k].size());

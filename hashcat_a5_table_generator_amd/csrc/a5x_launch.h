@@ -244,10 +244,10 @@ struct A5xHitRaw {  // (block, ordinal) until k_hits_resolve, then (word, candid
 struct A5xDigLaunch {
   const uint8_t* out;  // "cand\n" stream, 16-B aligned, starts at a candidate
   uint64_t nbytes;
-  int algo;            // A5X_ALGO_MD5 / A5X_ALGO_NTLM
+  int algo;            // A5X_ALGO_*
   const uint32_t* bitmap;
   uint32_t bm_mask;    // prefilter index mask: 2^k - 1 for a 2^k-bit bitmap (k <= 32)
-  const uint4* table;  // open addressing, all-zero = empty
+  const uint4* table;  // open addressing, all-zero = empty; the first 16 digest bytes
   uint64_t tmask;
   uint32_t has_zero_target;
   A5xHitRaw* hits;
@@ -255,11 +255,18 @@ struct A5xDigLaunch {
   uint32_t hit_cap;
   uint64_t* blk_cnt;        // op 1 output (per 2 KiB block line starts)
   const uint64_t* blk_pre;  // op 2 / resolve input (exclusive scan of blk_cnt)
-  uint8_t* dig_out;         // op 2 output: 16 B per candidate
+  uint8_t* dig_out;         // op 2 output: a5x_digest_size(algo) bytes per candidate
   uint32_t* err;
+  // wide algorithms (SHA-1: 1 tail word, SHA-256: 4): the digest words past the first
+  // four of every table slot, the tails of the targets whose first 16 bytes are zero
+  // (has_zero_target), and per hit the tail that matched (4 words each, hit order)
+  const uint32_t* tails;
+  const uint32_t* ztails;
+  uint32_t nztails;
+  uint32_t* hit_tail;
 };
 size_t a5x_digest_lds(int algo);
-uint64_t a5x_digest_blocks(uint64_t nbytes, int algo);  // 4 KiB (MD5) / 2 KiB (NTLM) blocks
+uint64_t a5x_digest_blocks(uint64_t nbytes, int algo);  // 2 KiB (NTLM) / 4 KiB (MD5, SHA-1, SHA-256) blocks
 hipError_t a5x_launch_digest_stream(const A5xDigLaunch& L, int op, uint32_t grid, hipStream_t st);
 // hybrid fused digest: list the candidate-bearing non-FAST words (n: device counter),
 // then gather them into a sub-batch (lens != null: their lengths; else the bytes at sub_off)

@@ -140,6 +140,43 @@ __device__ __forceinline__ bool md_probe(const uint32_t* bitmap, uint32_t bm_mas
   return false;
 }
 
+// Digests wider than 16 bytes (d = 4 + TW words): the same prefilter and table on the
+// first four words; slot s holds its remaining TW words at tails[TW * s].  A slot matches
+// only when both agree: on an equal prefix with another tail the probe goes on (two
+// targets may share their first 16 bytes).  Targets whose first four words are zero
+// (has_zero) have their tails in the side list ztails (nz entries).
+template <int TW>
+__device__ __forceinline__ bool md_probe_wide(const uint32_t* bitmap, uint32_t bm_mask, const uint4* table,
+                                              const uint32_t* tails, uint64_t tmask, bool has_zero,
+                                              const uint32_t* ztails, uint32_t nz, const uint32_t* d) {
+  if ((d[0] | d[1] | d[2] | d[3]) == 0u) {
+    if (!has_zero) return false;
+    for (uint32_t z = 0; z < nz; z++) {
+      uint32_t x = 0;
+#pragma unroll
+      for (int k = 0; k < TW; k++) x |= ztails[(uint64_t)TW * z + k] ^ d[4 + k];
+      if (x == 0u) return true;
+    }
+    return false;
+  }
+  if (!md_prefilter(bitmap, bm_mask, false, d[0], d[3])) return false;
+  const uint64_t h = ((uint64_t)d[1] | ((uint64_t)d[2] << 32)) * 0x9E3779B97F4A7C15ull;
+  uint64_t slot = (h >> 20) & tmask;
+  for (uint64_t n = 0; n <= tmask; n++) {
+    const uint4 e = table[slot];
+    if (e.x == d[0] && e.y == d[1] && e.z == d[2] && e.w == d[3]) {
+      uint32_t x = 0;
+#pragma unroll
+      for (int k = 0; k < TW; k++) x |= tails[slot * TW + k] ^ d[4 + k];
+      if (x == 0u) return true;
+    } else if ((e.x | e.y | e.z | e.w) == 0u) {
+      return false;
+    }
+    slot = (slot + 1) & tmask;
+  }
+  return false;
+}
+
 // One-block digest + probe with early rejection: steps 1-62 (MD4: 1-46) give digest words 0
 // and 3; when no lane of the wave passes the prefilter on them the last two steps and the
 // table probe are skipped (no hit is possible).  h = the digest (words 1, 2 only when the

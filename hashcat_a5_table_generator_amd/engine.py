@@ -36,8 +36,18 @@ MODE_SUBALL = 2
 MODE_SUBALL_REVERSE = 3
 ALGO_MD5 = 0   # RFC 1321 (Go crypto/md5)
 ALGO_NTLM = 1  # MD4 over UTF-16LE ([]rune + utf16.Encode)
+ALGO_SHA1 = 2  # FIPS 180-4 over the candidate bytes (hashcat -m 100)
+ALGO_SHA256 = 3  # FIPS 180-4 over the candidate bytes (hashcat -m 1400)
 
 SubMap = Dict[bytes, List[bytes]]
+
+
+def digest_size(algo: int) -> int:
+    """Digest bytes of an algorithm (``a5x_digest_size``): 16, 16, 20, 32."""
+    n = _lib.load().a5x_digest_size(algo)
+    if n < 0:
+        raise A5xError(n, f"bad digest algorithm {algo}")
+    return n
 
 
 def mode_of(substitute_all: bool, reverse_sub: bool) -> int:
@@ -213,20 +223,39 @@ class Context:
 
     # ---- fused digest + lookup ----------------------------------
     def set_targets(self, algo: int, digests) -> None:
-        """Device target set from 16-byte digests (bytes of length 16*n or an (n,16) uint8 array)."""
+        """Device target set from digests of ``digest_size(algo)`` bytes each (bytes of length
+        size*n or an (n, size) uint8 array)."""
         buf = np.ascontiguousarray(np.frombuffer(bytes(digests), dtype=np.uint8) if isinstance(digests, (bytes, bytearray))
                                    else np.asarray(digests, dtype=np.uint8)).reshape(-1)
-        if buf.size % 16:
-            raise ValueError("digests must be 16 bytes each")
-        self._chk(self._L.a5x_set_targets(self.h, algo, buf.ctypes.data if buf.size else None, buf.size // 16))
+        size = self._L.a5x_digest_size(algo)
+        if size <= 0:  # (a5x_set_targets names the bad algorithm)
+            size = 16
+        if buf.size % size:
+            raise ValueError(f"digests must be {size} bytes each")
+        self._chk(self._L.a5x_set_targets(self.h, algo, buf.ctypes.data if buf.size else None, buf.size // size))
+        self._algo_size = size
 
-    @staticmethod
-    def _hits(arr, n) -> List[Tuple[int, int, bytes]]:
-        return [(int(h.word), int(h.cand), bytes(h.digest)) for h in arr[:n]]
+    def hit_digest(self, hit) -> bytes:
+        """The full digest of a hit ``(word, cand, digest)`` against the current target set
+        (``a5x_hit_digest``): for SHA-1 / SHA-256 the target that the hit's 16 digest bytes begin."""
+        h = _lib.Hit()
+        h.word, h.cand = int(hit[0]), int(hit[1])
+        ctypes.memmove(h.digest, bytes(hit[2])[:16], 16)
+        out = (ctypes.c_uint8 * 32)()
+        n = ctypes.c_size_t()
+        self._chk(self._L.a5x_hit_digest(self.h, ctypes.byref(h), out, 32, ctypes.byref(n)))
+        return bytes(out[: n.value])
+
+    def _hits(self, arr, n) -> List[Tuple[int, int, bytes]]:
+        hits = [(int(h.word), int(h.cand), bytes(h.digest)) for h in arr[:n]]
+        if getattr(self, "_algo_size", 16) > 16:  # the full-width digest (a5x_hit_digest)
+            hits = [(w, c, self.hit_digest((w, c, d))) for w, c, d in hits]
+        return hits
 
     def expand_digest(self, words: np.ndarray, offs: np.ndarray, mode: int = MODE_DEFAULT, mn: int = 0,
                       mx: int = 15, hit_cap: int = 1 << 16) -> Tuple[List[Tuple[int, int, bytes]], dict]:
-        """Expand + hash + probe on the device; returns ([(word, cand_in_word, digest)], stats)."""
+        """Expand + hash + probe on the device; returns ([(word, cand_in_word, digest)], stats);
+        digest at the algorithm's full width."""
         arr = (_lib.Hit * max(1, hit_cap))()
         nh = ctypes.c_uint64()
         st = Stats()
@@ -261,11 +290,12 @@ class Context:
     def format_hits(self, words: np.ndarray, offs: np.ndarray, hits, mode: int = MODE_DEFAULT, mn: int = 0,
                     mx: int = 15) -> bytes:
         """hashcat "hexdigest:plain\\n" lines for hits [(word, cand, digest)] of this batch
-        (a5x_format_hits; plains in $HEX[] form when hashcat's outfile would hexify them)."""
+        (a5x_format_hits; plains in $HEX[] form when hashcat's outfile would hexify them).
+        digest: the full digest or its first 16 bytes (the library prints the full width)."""
         arr = (_lib.Hit * max(1, len(hits)))()
         for k, (w, c, d) in enumerate(hits):
             arr[k].word, arr[k].cand = int(w), int(c)
-            ctypes.memmove(arr[k].digest, bytes(d), 16)
+            ctypes.memmove(arr[k].digest, bytes(d)[:16], 16)
         chunks: List[bytes] = []
 
         def _cb(_u, p, n):
@@ -279,7 +309,8 @@ class Context:
 
     def digest_lines_device(self, algo: int, d_lines: int, nbytes: int, d_digests: int, cap: int,
                             stream: int = 0) -> int:
-        """16-byte digest of every line of a device "cand\n" stream; returns the line count."""
+        """Digest of every line of a device "cand\n" stream, ``digest_size(algo)`` bytes per line
+        in line order (cap counts lines); returns the line count."""
         n = ctypes.c_uint64()
         self._chk(self._L.a5x_digest_lines_device(self.h, algo, d_lines, nbytes, d_digests or None, cap,
                                                   ctypes.byref(n), stream or None))

@@ -5,7 +5,9 @@ opcode (tools/mb_valu.hip, profiles/r06_mb_valu.txt, 4 waves per SIMD): v_add_u3
 v_bitop3_b32 / v_add_u32_e64 / v_cmp / v_cndmask issue in ~2 cycles (the chip's nominal
 32 lanes per cycle), v_add3_u32 / v_alignbit_b32 / v_bfi_b32 / v_perm_b32 / v_alignbyte_b32 /
 v_lshl_or_b32 / v_lshl_add_u32 / v_lshlrev_b32_e64 / v_mul_hi_u32 in ~4 (half rate).
-This tool compiles md5_block / md4_block (csrc/a5x_md.h) on runtime data and the whole
+This tool compiles md5_block / md4_block (csrc/a5x_md.h) and sha1_block / sha256_block
+(csrc/a5x_sha.h; per 64-byte block, with the 16 byte swaps of its message words) on runtime
+data and the whole
 k_expand_fast_md5 / _ntlm kernels, counts every VALU opcode and prices it, giving the mean
 SIMD cycles per VALU instruction of each stream -> the mix-weighted VALU peak
 (256 CUs x 4 SIMDs x 64 lanes x clock / mean cycles) that bench.py reports beside the nominal
@@ -45,6 +47,7 @@ def price(op):
 PROBE = r'''
 #include <hip/hip_runtime.h>
 #include "a5x_md.h"
+#include "a5x_sha.h"
 __global__ void p_md5(const uint32_t* in, uint32_t* out) {
   uint32_t M[16], st[4] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u};
   for (int i = 0; i < 16; i++) M[i] = in[threadIdx.x * 16 + i];
@@ -56,6 +59,19 @@ __global__ void p_md4(const uint32_t* in, uint32_t* out) {
   for (int i = 0; i < 16; i++) M[i] = in[threadIdx.x * 16 + i];
   md4_block(st, M);
   for (int i = 0; i < 4; i++) out[threadIdx.x * 4 + i] = st[i];
+}
+__global__ void p_sha1(const uint32_t* in, uint32_t* out) {
+  uint32_t M[16], st[5] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u, 0xc3d2e1f0u};
+  for (int i = 0; i < 16; i++) M[i] = sha_bswap(in[threadIdx.x * 16 + i]);
+  sha1_block(st, M);
+  for (int i = 0; i < 5; i++) out[threadIdx.x * 5 + i] = st[i];
+}
+__global__ void p_sha256(const uint32_t* in, uint32_t* out) {
+  uint32_t M[16], st[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu,
+                           0x5be0cd19u};
+  for (int i = 0; i < 16; i++) M[i] = sha_bswap(in[threadIdx.x * 16 + i]);
+  sha256_block(st, M);
+  for (int i = 0; i < 8; i++) out[threadIdx.x * 8 + i] = st[i];
 }
 '''
 
@@ -91,7 +107,8 @@ def main():
     p = os.path.join(d, "probe.hip")
     open(p, "w").write(PROBE)
     t = asm(p)
-    res = {"md5_block": mix(func_ops(t, "_Z5p_md5PKjPj")), "md4_block": mix(func_ops(t, "_Z5p_md4PKjPj"))}
+    res = {"md5_block": mix(func_ops(t, "_Z5p_md5PKjPj")), "md4_block": mix(func_ops(t, "_Z5p_md4PKjPj")),
+           "sha1_block": mix(func_ops(t, "_Z6p_sha1PKjPj")), "sha256_block": mix(func_ops(t, "_Z8p_sha256PKjPj"))}
     k = asm(os.path.join(CSRC, "a5x_kernels.hip"))
     res["k_expand_fast_md5 (static, whole kernel)"] = mix(func_ops(k, "_Z17k_expand_fast_md57ExpArgs"))
     res["k_expand_fast_ntlm (static, whole kernel)"] = mix(func_ops(k, "_Z18k_expand_fast_ntlm7ExpArgs"))
