@@ -32,6 +32,8 @@ EXPORTS = (
     "a5x_digest_lines_device", "a5x_digest_size", "a5x_hit_digest", "a5x_debug_digest",
     "a5x_format_plain", "a5x_format_hits", "a5x_locate_device", "a5x_split_device",
     "a5x_stream_reserve",
+    "a5x_set_rules", "a5x_load_rules_file", "a5x_rule_count", "a5x_hit_rules", "a5x_rules_last",
+    "a5x_format_hits_rules", "a5x_digest_lines_rules_device", "a5x_debug_apply_rule",
 )
 
 
@@ -123,6 +125,14 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     L.a5x_locate_device.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, vp]
     L.a5x_stream_reserve.argtypes = [vp, u64, u64]
     L.a5x_split_device.argtypes = [vp, vp, vp, u64, i, i, i, vp, u32, vp, vp, vp, vp]
+    L.a5x_set_rules.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.a5x_load_rules_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.a5x_rule_count.argtypes = [vp]
+    L.a5x_hit_rules.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.a5x_rules_last.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.a5x_format_hits_rules.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, SINK, vp]
+    L.a5x_digest_lines_rules_device.argtypes = [vp, i, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
+    L.a5x_debug_apply_rule.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz)]
     _lib = L
     return L
 

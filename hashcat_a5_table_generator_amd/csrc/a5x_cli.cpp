@@ -6,7 +6,7 @@
 //
 //   a5x_generator <dict-file> -t <table> [-t <table> ...] [-m N] [-x N]
 //                 [--threads N] [-s] [-r] [--device N]
-//                 [--hashes <file> [--algo md5|ntlm|sha1|sha256]]
+//                 [--hashes <file> [--algo md5|ntlm|sha1|sha256] [--rules <file>]]
 //                 [--skip N] [--limit N] [--keyspace]
 //
 // --hashes (a5x extension): instead of printing the candidates for a
@@ -56,6 +56,8 @@ static void usage(FILE* f) {
           "  -r, --reverse-sub                 Reverse substitution direction\n"
           "      --device=0                    GPU ordinal (a5x extension)\n"
           "      --hashes=FILE                 Crack: print hash:plain for the digests in FILE (a5x extension)\n"
+          "      --rules=FILE                  With --hashes: apply every hashcat rule of FILE to each candidate\n"
+          "                                    before hashing (hashcat -r; long form only: -r is --reverse-sub)\n"
           "      --algo=md5                    Digest of --hashes: md5 (hashcat -m 0), ntlm (-m 1000),\n"
           "                                    sha1 (-m 100) or sha256 (-m 1400)\n"
           "      --skip=0                      Resume: start at candidate N of the stream (a5x extension)\n"
@@ -287,7 +289,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> tables;
   std::string dict;
   int tmin = 0, tmax = 15, threads = -1, device = 0, algo = A5X_ALGO_MD5;
-  std::string hashes;
+  std::string hashes, rules;
   bool suball = false, rev = false, keyspace_only = false, cursor = false;
   uint64_t skip = 0, limit = ~0ull;
   auto need = [&](int& i, const char* flag) -> const char* {
@@ -333,6 +335,8 @@ int main(int argc, char** argv) {
       device = v;
     } else if (s.rfind("--hashes", 0) == 0) {
       hashes = val_of("--hashes");
+    } else if (s.rfind("--rules", 0) == 0) {
+      rules = val_of("--rules");
     } else if (s.rfind("--algo", 0) == 0) {
       std::string v = val_of("--algo");
       if (v == "md5" || v == "0") algo = A5X_ALGO_MD5;
@@ -375,6 +379,10 @@ int main(int argc, char** argv) {
   if (const char* e = getenv("A5X_CLI_CHUNK")) chunk = std::max<size_t>(1, strtoull(e, nullptr, 10));
   static char obuf[1 << 22];
   setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
+  if (!rules.empty() && hashes.empty()) {
+    fprintf(stderr, "a5_generator: error: --rules applies to the digest + lookup stage: it needs --hashes\n");
+    return 80;
+  }
   if (!hashes.empty() && (cursor || keyspace_only)) {
     fprintf(stderr, "a5_generator: error: --skip / --limit / --keyspace select the candidate stream, not --hashes\n");
     return 80;
@@ -514,6 +522,24 @@ int main(int argc, char** argv) {
     fclose(f);
     return 1;
   }
+  uint64_t rejected = 0;
+  if (!rules.empty()) {
+    uint32_t nr = 0, nsk = 0;
+    if ((rc = a5x_load_rules_file(ctx, rules.c_str(), &nr, &nsk))) {
+      fprintf(stderr, "a5_generator: %s\n", rc == A5X_E_IO ? "cannot read --rules file" : a5x_last_error(ctx));
+      a5x_destroy(ctx);
+      fclose(f);
+      return 1;
+    }
+    fprintf(stderr, "a5_generator: rules: %u accepted, %u line(s) skipped (unsupported or malformed)\n", nr, nsk);
+    if (!nr) {
+      fprintf(stderr, "a5_generator: error: no usable rule in %s\n", rules.c_str());
+      a5x_destroy(ctx);
+      fclose(f);
+      return 1;
+    }
+  }
+  const bool ruled = !rules.empty();
   DictStream ds(f, chunk);
   std::vector<uint8_t> words;
   std::vector<uint64_t> sub;
@@ -529,21 +555,43 @@ int main(int argc, char** argv) {
       rc = a5x_expand_digest(ctx, wb, sub.data(), nb, mode, tmin, tmax, hits.data(), hits.size(), &nh, nullptr);
     }
     if (rc) break;
-    // stream order, then the first candidate of each digest
-    std::sort(hits.begin(), hits.begin() + nh, [](const a5x_hit& x, const a5x_hit& y) {
-      return x.word != y.word ? x.word < y.word : x.cand < y.cand;
+    std::vector<uint32_t> hrule(nh, 0u);  // ruled: each hit's rule, carried through the sort
+    if (ruled) {
+      uint64_t nr = 0, rej = 0;
+      if ((rc = a5x_hit_rules(ctx, hrule.data(), hrule.size(), &nr)) || (rc = a5x_rules_last(ctx, nullptr, &rej))) break;
+      rejected += rej;
+    }
+    // stream order (then rule order), then the first candidate of each digest
+    std::vector<uint64_t> ord(nh);
+    for (uint64_t h = 0; h < nh; h++) ord[h] = h;
+    std::sort(ord.begin(), ord.end(), [&](uint64_t x, uint64_t y) {
+      if (hits[x].word != hits[y].word) return hits[x].word < hits[y].word;
+      if (hits[x].cand != hits[y].cand) return hits[x].cand < hits[y].cand;
+      return hrule[x] < hrule[y];
     });
     std::vector<a5x_hit> first;
-    for (uint64_t h = 0; h < nh && rc == 0; h++) {  // keyed on the full digest (20 / 32 bytes for SHA-1 / SHA-256)
+    std::vector<uint32_t> first_rule;
+    for (uint64_t k = 0; k < nh && rc == 0; k++) {  // keyed on the full digest (20 / 32 bytes for SHA-1 / SHA-256)
+      const uint64_t h = ord[k];
       uint8_t full[32];
       size_t fl = 0;
       if ((rc = a5x_hit_digest(ctx, &hits[h], full, sizeof full, &fl))) break;
-      if (cracked.insert(std::string((const char*)full, fl)).second) first.push_back(hits[h]);
+      if (cracked.insert(std::string((const char*)full, fl)).second) {
+        first.push_back(hits[h]);
+        first_rule.push_back(hrule[h]);
+      }
     }
     if (rc) break;
-    rc = a5x_format_hits(ctx, wb, sub.data(), nb, mode, tmin, tmax, first.data(), first.size(), sink_stdout,
-                         nullptr);
+    if (ruled)
+      rc = a5x_format_hits_rules(ctx, wb, sub.data(), nb, mode, tmin, tmax, first.data(), first.size(),
+                                 first_rule.data(), sink_stdout, nullptr);
+    else
+      rc = a5x_format_hits(ctx, wb, sub.data(), nb, mode, tmin, tmax, first.data(), first.size(), sink_stdout,
+                           nullptr);
   }
+  if (ruled)
+    fprintf(stderr, "a5_generator: rules: %llu candidate(s) longer than 128 bytes rejected\n",
+            (unsigned long long)rejected);
   fclose(f);
   fflush(stdout);
   if (rc) fprintf(stderr, "a5_generator: %s\n", a5x_last_error(ctx));

@@ -30,6 +30,7 @@
 #include "a5x_gosem.h"
 #include "a5x_launch.h"
 #include "a5x_md.h"
+#include "a5x_rules.h"
 #include "a5x_sha.h"
 
 namespace {
@@ -132,6 +133,15 @@ struct a5x_ctx {
   bool t_shared_prefix = false;
   std::map<std::pair<uint64_t, uint64_t>, std::array<uint32_t, 4>> t_hit_tails;
   hipEvent_t dev_ev[2] = {nullptr, nullptr};
+  // rules (a5x_rules.hip): the accepted rules as a table of A5X_RULE_STRIDE u32 each (host
+  // copy + device copy), and of the latest digest call: each copied hit's rule, the lines
+  // rejected as longer than A5X_RULE_LMAX, the hashes computed
+  std::vector<uint32_t> r_rules;
+  uint32_t n_rules = 0;
+  DevBuf<uint32_t> r_table, dg_hit_rule;
+  DevBuf<unsigned long long> r_counter;
+  std::vector<uint32_t> r_hit_rule;
+  uint64_t r_rejected = 0, r_hashed = 0;
 
   DevBuf<uint64_t> count, bytes, cand_off, byte_off, scan_tmp, locate;
   DevBuf<uint32_t> flags, defer, chunk_w0, slow_list, big_list, roff, cplx;
@@ -1442,6 +1452,11 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
     allow_fused = false;
     c->t_hit_tails.clear();
   }
+  // rules loaded: the two-pass range loop too, k_rules_stream in place of k_digest_stream op 0
+  const bool ruled = c->n_rules != 0;
+  if (ruled) allow_fused = false;
+  c->r_hit_rule.clear();
+  c->r_rejected = c->r_hashed = 0;
   Job J;
   job_open(c, J, d_words, d_woff, nw, mode, mn, mx, st);
   J.lengths = mode == A5X_MODE_DEFAULT || !allow_fused;  // the fused -r / -s digest needs no layout
@@ -1640,6 +1655,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   uint64_t dev_hits = std::max<uint64_t>(1024, std::min<uint64_t>(hit_cap, 1u << 20));
   if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
   if (wide && (rc = grow(c, c->dg_hit_tail, 4 * dev_hits))) return rc;
+  if (ruled && ((rc = grow(c, c->dg_hit_rule, dev_hits)) || (rc = grow(c, c->r_counter, 2)))) return rc;
   std::vector<uint32_t> htail;  // wide: the range's hit tails
   a5x_stats total;
   memset(&total, 0, sizeof total);
@@ -1658,12 +1674,13 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
     A5xDigLaunch D = dig_launch(c);
     D.out = c->dg_scratch.p;
     D.nbytes = R.b1 - R.b0;
-    const uint64_t nblk = a5x_digest_blocks(D.nbytes, D.algo);
+    const uint64_t nblk = ruled ? a5x_rules_blocks(D.nbytes) : a5x_digest_blocks(D.nbytes, D.algo);
     if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
         (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)))
       return rc;
     D.blk_cnt = c->dg_blk_cnt.p;
     uint64_t nh = 0;
+    unsigned long long rej = 0;  // ruled: the range's lines longer than A5X_RULE_LMAX
     {
       float me = 0;  // the range's expansion, once (a retry below re-runs only the digest)
       HIPCHK(c, hipEventSynchronize(c->ev[2]));
@@ -1676,10 +1693,22 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       D.hit_cap = (uint32_t)dev_hits;
       D.nhits = c->d_scalars + 8;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 8, 0, 4, J.st));
+      if (ruled) HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, J.st));
       HIPCHK(c, hipEventRecord(c->dev_ev[0], J.st));
-      HIPCHK(c, a5x_launch_digest_stream(D, 0, dig_grid(c), J.st));
+      if (ruled) {
+        A5xRuleLaunch RL;
+        RL.d = D;
+        RL.rules = c->r_table.p;
+        RL.nrules = c->n_rules;
+        RL.hit_rule = c->dg_hit_rule.p;
+        RL.rejected = c->r_counter.p;
+        HIPCHK(c, a5x_launch_rules_stream(RL, 0, (uint32_t)std::max(1, c->cus), J.st));
+      } else {
+        HIPCHK(c, a5x_launch_digest_stream(D, 0, dig_grid(c), J.st));
+      }
       HIPCHK(c, hipEventRecord(c->dev_ev[1], J.st));
       HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, J.st));
+      if (ruled) HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, J.st));
       HIPCHK(c, hipStreamSynchronize(J.st));
       float md = 0;
       HIPCHK(c, hipEventElapsedTime(&md, c->dev_ev[0], c->dev_ev[1]));
@@ -1691,7 +1720,13 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       dev_hits = nh;  // grow and run this range's digest again (its candidates are still in scratch)
       if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
       if (wide && (rc = grow(c, c->dg_hit_tail, 4 * dev_hits))) return rc;
+      if (ruled && (rc = grow(c, c->dg_hit_rule, dev_hits))) return rc;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 2, 0, 4, J.st));
+    }
+    if (ruled) {
+      if (rej > R.ce - R.cb) return fail(c, A5X_E_HIP, "more rejected lines than the range has candidates");
+      c->r_rejected += rej;
+      c->r_hashed += (R.ce - R.cb - rej) * c->n_rules;
     }
     if (nh) {
       const uint64_t got = std::min<uint64_t>(nh, dev_hits);
@@ -1705,6 +1740,10 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       if (take && c->t_shared_prefix) {
         htail.resize(4 * take);
         HIPCHK(c, hipMemcpyAsync(htail.data(), c->dg_hit_tail.p, take * 16, hipMemcpyDeviceToHost, J.st));
+      }
+      if (take && ruled) {
+        c->r_hit_rule.resize(copied + take);
+        HIPCHK(c, hipMemcpyAsync(c->r_hit_rule.data() + copied, c->dg_hit_rule.p, take * 4, hipMemcpyDeviceToHost, J.st));
       }
       HIPCHK(c, hipStreamSynchronize(J.st));
       if (take && c->t_shared_prefix)  // (which of the targets sharing a prefix each hit matched: a5x_hit_digest)
@@ -1825,6 +1864,7 @@ void a5x_destroy(a5x_ctx* c) {
   release(c->t_bitmap); release(c->t_table); release(c->dg_scratch); release(c->dg_blk_cnt); release(c->dg_blk_pre);
   release(c->dg_cand_off); release(c->dg_byte_off); release(c->dg_hits);
   release(c->t_tails); release(c->t_ztails); release(c->dg_hit_tail);
+  release(c->r_table); release(c->dg_hit_rule); release(c->r_counter);
   release(c->hy_list); release(c->hy_lens); release(c->hy_off); release(c->hy_words);
   for (auto& e : c->dev_ev)
     if (e) (void)hipEventDestroy(e);
@@ -2574,8 +2614,10 @@ int a5x_format_plain(const uint8_t* plain, size_t len, uint8_t* out, size_t cap,
   return A5X_OK;
 }
 
-int a5x_format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw, int mode, int mn, int mx,
-                    const a5x_hit* hits, uint64_t n_hits, a5x_sink_fn sink, void* user) {
+// a5x_format_hits, and with hit_rule a5x_format_hits_rules: each regenerated plain goes
+// through its hit's rule on the host (the interpreter the kernel ran)
+static int format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw, int mode, int mn, int mx,
+                       const a5x_hit* hits, uint64_t n_hits, const uint32_t* hit_rule, a5x_sink_fn sink, void* user) {
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || !sink || (n_hits && (!hits || !words || !woff))) return A5X_E_ARG;
   if (!n_hits) return A5X_OK;
@@ -2698,13 +2740,177 @@ int a5x_format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint
       o += hx[full[(size_t)dsz * h + i] & 15];
     }
     o += ':';
-    append_plain(o, (const uint8_t*)plain[k].data(), plain[k].size());
+    if (hit_rule) {
+      if (hit_rule[h] >= c->n_rules) return fail(c, A5X_E_ARG, "hit rule %u of %u loaded", hit_rule[h], c->n_rules);
+      if (plain[k].size() > A5X_RULE_LMAX) return fail(c, A5X_E_ARG, "hit candidate longer than the rule limit");
+      RuleFlat b;
+      memset(&b, 0, sizeof b);
+      memcpy(b.w, plain[k].data(), plain[k].size());
+      const uint32_t* ops = &c->r_rules[(size_t)hit_rule[h] * A5X_RULE_STRIDE];
+      const uint32_t L = rule_apply(b, (uint32_t)plain[k].size(), ops + 1, ops[0]);
+      append_plain(o, (const uint8_t*)b.w, L);
+    } else {
+      append_plain(o, (const uint8_t*)plain[k].data(), plain[k].size());
+    }
     o += '\n';
     if (o.size() >= (1u << 20) || h + 1 == n_hits) {
       if (sink(user, (const uint8_t*)o.data(), o.size())) return fail(c, A5X_E_SINK, "sink returned non-zero");
       o.clear();
     }
   }
+  return A5X_OK;
+}
+
+int a5x_format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw, int mode, int mn, int mx,
+                    const a5x_hit* hits, uint64_t n_hits, a5x_sink_fn sink, void* user) {
+  return format_hits(c, words, woff, nw, mode, mn, mx, hits, n_hits, nullptr, sink, user);
+}
+
+int a5x_format_hits_rules(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw, int mode, int mn,
+                          int mx, const a5x_hit* hits, uint64_t n_hits, const uint32_t* hit_rule, a5x_sink_fn sink,
+                          void* user) {
+  if (c && n_hits && !hit_rule) return fail(c, A5X_E_ARG, "no rule indices");
+  return format_hits(c, words, woff, nw, mode, mn, mx, hits, n_hits, hit_rule, sink, user);
+}
+
+// ---- rules (a5x_rules.h, a5x_rules.hip) -----------------------------------------
+int a5x_set_rules(a5x_ctx* c, const uint8_t* text, size_t len, uint32_t* n_rules, uint32_t* n_skipped) {
+  if (!c || (len && !text)) return A5X_E_ARG;
+  std::vector<uint32_t> tab;
+  uint32_t nr = 0, ns = 0;
+  for (size_t p = 0; p < len;) {
+    size_t e = p;
+    while (e < len && text[e] != '\n') e++;
+    uint32_t ops[A5X_RULE_OPS_MAX], nops = 0;
+    const int k = rule_parse_line(text + p, e - p, ops, &nops);
+    if (k == RULE_LINE_SKIPPED) ns++;
+    if (k == RULE_LINE_OK) {
+      tab.resize((size_t)(nr + 1) * A5X_RULE_STRIDE, 0u);
+      tab[(size_t)nr * A5X_RULE_STRIDE] = nops;
+      memcpy(&tab[(size_t)nr * A5X_RULE_STRIDE + 1], ops, nops * sizeof(uint32_t));
+      nr++;
+    }
+    p = e + 1;
+  }
+  if (c->device >= 0 && nr) {
+    int rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (no kernel of an earlier call still reads the table)
+    if ((rc = grow(c, c->r_table, tab.size()))) return rc;
+    HIPCHK(c, hipMemcpy(c->r_table.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  }
+  c->r_rules.swap(tab);
+  c->n_rules = nr;
+  c->r_hit_rule.clear();
+  if (n_rules) *n_rules = nr;
+  if (n_skipped) *n_skipped = ns;
+  return A5X_OK;
+}
+
+int a5x_load_rules_file(a5x_ctx* c, const char* path, uint32_t* n_rules, uint32_t* n_skipped) {
+  if (!c || !path) return A5X_E_ARG;
+  FILE* f = fopen(path, "rb");
+  if (!f) return fail(c, A5X_E_IO, "open %s: %s", path, strerror(errno));
+  std::vector<uint8_t> d;
+  uint8_t buf[1 << 16];
+  size_t n;
+  while ((n = fread(buf, 1, sizeof buf, f)) > 0) d.insert(d.end(), buf, buf + n);
+  const bool bad = ferror(f) != 0;
+  fclose(f);
+  if (bad) return fail(c, A5X_E_IO, "read %s failed", path);
+  return a5x_set_rules(c, d.data(), d.size(), n_rules, n_skipped);
+}
+
+int a5x_rule_count(const a5x_ctx* c) { return c ? (int)c->n_rules : A5X_E_ARG; }
+
+int a5x_hit_rules(a5x_ctx* c, uint32_t* rule_out, uint64_t cap, uint64_t* n) {
+  if (!c || !n) return A5X_E_ARG;
+  *n = c->r_hit_rule.size();
+  if (!rule_out) return A5X_OK;
+  if (cap < c->r_hit_rule.size())
+    return fail(c, A5X_E_CAPACITY, "%zu hit rules, buffer has %llu", c->r_hit_rule.size(), (unsigned long long)cap);
+  if (!c->r_hit_rule.empty()) memcpy(rule_out, c->r_hit_rule.data(), c->r_hit_rule.size() * 4);
+  return A5X_OK;
+}
+
+int a5x_rules_last(a5x_ctx* c, uint64_t* hashed, uint64_t* rejected) {
+  if (!c) return A5X_E_ARG;
+  if (hashed) *hashed = c->r_hashed;
+  if (rejected) *rejected = c->r_rejected;
+  return A5X_OK;
+}
+
+int a5x_digest_lines_rules_device(a5x_ctx* c, int algo, const uint8_t* d_lines, uint64_t nbytes, uint8_t* d_dig,
+                                  uint64_t cap, uint64_t* n_lines, void* stream) {
+  if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
+  if (!c || (nbytes && !d_lines)) return A5X_E_ARG;
+  if (!algo_size(algo)) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
+  if (!c->n_rules) return fail(c, A5X_E_ARG, "no rules loaded (a5x_set_rules)");
+  if (((uintptr_t)d_lines & 15u) != 0) return fail(c, A5X_E_ARG, "d_lines must be 16-byte aligned");
+  if (((uintptr_t)d_dig & 3u) != 0) return fail(c, A5X_E_ARG, "d_digests must be 4-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (n_lines) *n_lines = 0;
+  c->r_rejected = c->r_hashed = 0;
+  c->r_hit_rule.clear();
+  if (!nbytes) return A5X_OK;
+  int rc;
+  const uint64_t nblk = a5x_rules_blocks(nbytes);
+  if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
+      (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)) || (rc = grow(c, c->r_counter, 2)))
+    return rc;
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 64, st));
+  HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, st));
+  A5xRuleLaunch RL;
+  RL.d = dig_launch(c);
+  RL.d.algo = algo;
+  RL.d.out = d_lines;
+  RL.d.nbytes = nbytes;
+  RL.d.blk_cnt = c->dg_blk_cnt.p;
+  RL.rules = c->r_table.p;
+  RL.nrules = c->n_rules;
+  RL.hit_rule = nullptr;
+  RL.rejected = c->r_counter.p;
+  HIPCHK(c, a5x_launch_rules_stream(RL, 1, (uint32_t)std::max(1, c->cus), st));
+  HIPCHK(c, a5x_launch_scan(c->dg_blk_cnt.p, c->dg_blk_cnt.p, nblk, c->dg_blk_pre.p, c->dg_blk_pre.p, c->scan_tmp.p,
+                            c->d_scalars + 2, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_totals + 2, c->dg_blk_pre.p + nblk, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const uint64_t lines = c->h_totals[2];
+  if (n_lines) *n_lines = lines;
+  if (lines > cap / c->n_rules || !d_dig)
+    return fail(c, A5X_E_CAPACITY, "%llu lines x %u rules, digest buffer has room for %llu", (unsigned long long)lines,
+                c->n_rules, (unsigned long long)cap);
+  RL.d.blk_cnt = nullptr;
+  RL.d.blk_pre = c->dg_blk_pre.p;
+  RL.d.dig_out = d_dig;
+  HIPCHK(c, a5x_launch_rules_stream(RL, 2, (uint32_t)std::max(1, c->cus), st));
+  unsigned long long rej = 0;
+  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (rej > lines) return fail(c, A5X_E_HIP, "more rejected lines than lines");
+  c->r_rejected = rej;
+  c->r_hashed = (lines - rej) * c->n_rules;
+  return decode_dev_err(c, c->h_scalars[2]);
+}
+
+int a5x_debug_apply_rule(const uint8_t* rule, size_t rule_len, const uint8_t* word, size_t len, uint8_t* out,
+                         size_t cap, size_t* out_len) {
+  if ((!rule && rule_len) || (!word && len) || !out_len || len > A5X_RULE_LMAX) return A5X_E_ARG;
+  uint32_t ops[A5X_RULE_OPS_MAX], nops = 0;
+  if (rule_parse_line(rule, rule_len, ops, &nops) != RULE_LINE_OK) return A5X_E_ARG;
+  RuleFlat b;
+  memset(&b, 0, sizeof b);
+  if (len) memcpy(b.w, word, len);
+  const uint32_t L = rule_apply(b, (uint32_t)len, ops, nops);
+  // (test hook: the zero-past-the-word invariant of a5x_rules.h holds after every rule)
+  for (uint32_t i = L; i < 4u * A5X_RULE_NDW; i++)
+    if (((const uint8_t*)b.w)[i]) return A5X_E_BOUNDS;
+  *out_len = L;
+  if (!out) return A5X_OK;
+  if (cap < L) return A5X_E_CAPACITY;
+  memcpy(out, b.w, L);
   return A5X_OK;
 }
 

@@ -276,3 +276,18 @@ hipError_t a5x_launch_gather_words(const uint8_t* words, const uint64_t* woff, c
                                    uint64_t* lens, const uint64_t* sub_off, uint8_t* out, hipStream_t st);
 hipError_t a5x_launch_hits_resolve(A5xHitRaw* hits, uint32_t n, const uint64_t* blk_pre, uint64_t cand_base,
                                    const uint64_t* cand_off, uint64_t nw, hipStream_t st);
+
+// ---- rules in the digest + lookup stage (a5x_rules.hip) -----------------------
+struct A5xRuleLaunch {
+  A5xDigLaunch d;                // the stream, target set and hit buffer, as k_digest_stream (blocks of 4 KiB)
+  const uint32_t* rules;         // nrules x A5X_RULE_STRIDE u32: function count, then the encoded functions
+  uint32_t nrules;
+  uint32_t* hit_rule;            // op 0: the rule index of hit h, beside d.hits
+  unsigned long long* rejected;  // += lines longer than A5X_RULE_LMAX (hashed under no rule)
+};
+size_t a5x_rules_lds();
+uint64_t a5x_rules_blocks(uint64_t nbytes);
+// op 0: hash + probe every (line, rule); op 1: line starts per block (d.blk_cnt); op 2: every
+// digest to d.dig_out at index line * nrules + rule (a rejected line's are zero)
+// (cus: the device's compute units; the grid is cus x the workgroups a CU holds at once)
+hipError_t a5x_launch_rules_stream(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st);

@@ -287,11 +287,62 @@ class Context:
                 scratch_bytes, arr, hit_cap, ctypes.byref(nh), ctypes.byref(st), stream or None))
         return self._hits(arr, min(nh.value, hit_cap)), st.as_dict()
 
+    # ---- rules in the digest + lookup stage (a5x_rules.hip) ------------------------
+    def set_rules(self, text_or_lines) -> Tuple[int, int]:
+        """Replace the rule set from rule-file text (bytes / str) or a sequence of rule lines;
+        returns (accepted, skipped).  While >= 1 rule is loaded every expand_digest* call
+        hashes each candidate once per rule; ``last_hit_rules()`` names each hit's rule."""
+        if isinstance(text_or_lines, str):
+            text = text_or_lines.encode()
+        elif isinstance(text_or_lines, (bytes, bytearray)):
+            text = bytes(text_or_lines)
+        else:
+            text = b"".join((l.encode() if isinstance(l, str) else bytes(l)) + b"\n" for l in text_or_lines)
+        n, sk = ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(self._L.a5x_set_rules(self.h, text, len(text), ctypes.byref(n), ctypes.byref(sk)))
+        return n.value, sk.value
+
+    def load_rules_file(self, path: str) -> Tuple[int, int]:
+        n, sk = ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(self._L.a5x_load_rules_file(self.h, os.fsencode(path), ctypes.byref(n), ctypes.byref(sk)))
+        return n.value, sk.value
+
+    def clear_rules(self) -> None:
+        self._chk(self._L.a5x_set_rules(self.h, None, 0, None, None))
+
+    def rule_count(self) -> int:
+        return self._L.a5x_rule_count(self.h)
+
+    def last_hit_rules(self) -> List[int]:
+        """Rule index of each hit the latest expand_digest* call returned, in hit order."""
+        n = ctypes.c_uint64()
+        self._chk(self._L.a5x_hit_rules(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(1, n.value), dtype=np.uint32)
+        self._chk(self._L.a5x_hit_rules(self.h, out.ctypes.data, out.size, ctypes.byref(n)))
+        return [int(x) for x in out[: n.value]]
+
+    def rules_last(self) -> Tuple[int, int]:
+        """(hashes computed, candidates rejected as longer than 128 bytes) of the latest ruled call."""
+        h, r = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._L.a5x_rules_last(self.h, ctypes.byref(h), ctypes.byref(r)))
+        return h.value, r.value
+
+    def digest_lines_rules_device(self, algo: int, d_lines: int, nbytes: int, d_digests: int, cap: int,
+                                  stream: int = 0) -> int:
+        """Digest of every (line, rule) of a device "cand\\n" stream under the loaded rules, at
+        index line * R + rule (cap counts digests; a line over 128 bytes gives R zero digests);
+        returns the line count."""
+        n = ctypes.c_uint64()
+        self._chk(self._L.a5x_digest_lines_rules_device(self.h, algo, d_lines, nbytes, d_digests or None, cap,
+                                                        ctypes.byref(n), stream or None))
+        return n.value
+
     def format_hits(self, words: np.ndarray, offs: np.ndarray, hits, mode: int = MODE_DEFAULT, mn: int = 0,
-                    mx: int = 15) -> bytes:
+                    mx: int = 15, rules=None) -> bytes:
         """hashcat "hexdigest:plain\\n" lines for hits [(word, cand, digest)] of this batch
         (a5x_format_hits; plains in $HEX[] form when hashcat's outfile would hexify them).
-        digest: the full digest or its first 16 bytes (the library prints the full width)."""
+        digest: the full digest or its first 16 bytes (the library prints the full width).
+        rules: each hit's rule index (``last_hit_rules()``): the plain printed is the ruled one."""
         arr = (_lib.Hit * max(1, len(hits)))()
         for k, (w, c, d) in enumerate(hits):
             arr[k].word, arr[k].cand = int(w), int(c)
@@ -303,6 +354,14 @@ class Context:
             return 0
 
         cb = _lib.SINK(_cb)
+        if rules is not None:
+            ra = np.ascontiguousarray(rules, dtype=np.uint32)
+            if ra.size != len(hits):
+                raise ValueError("one rule index per hit")
+            self._chk(self._L.a5x_format_hits_rules(self.h, words.ctypes.data, offs.ctypes.data, len(offs) - 1, mode,
+                                                    mn, mx, arr, len(hits), ra.ctypes.data if ra.size else None, cb,
+                                                    None))
+            return b"".join(chunks)
         self._chk(self._L.a5x_format_hits(self.h, words.ctypes.data, offs.ctypes.data, len(offs) - 1, mode, mn, mx,
                                           arr, len(hits), cb, None))
         return b"".join(chunks)
@@ -368,6 +427,21 @@ def format_plain(plain: bytes) -> bytes:
     out = ctypes.create_string_buffer(max(1, n.value))
     check(L.a5x_format_plain(plain, len(plain), out, n.value, ctypes.byref(n)))
     return out.raw[:n.value]
+
+
+def apply_rule(rule: bytes, word: bytes) -> bytes:
+    """One rule line applied to word on the host by the interpreter the rules kernel runs
+    (``a5x_debug_apply_rule``); ValueError for a line ``set_rules`` would skip."""
+    rule = rule.encode() if isinstance(rule, str) else bytes(rule)
+    word = bytes(word)
+    L = _lib.load()
+    out = (ctypes.c_uint8 * 136)()
+    n = ctypes.c_size_t()
+    rc = L.a5x_debug_apply_rule(rule, len(rule), word, len(word), out, 136, ctypes.byref(n))
+    if rc == -1:
+        raise ValueError(f"unsupported or malformed rule {rule!r} (or a word over 128 bytes)")
+    check(rc)
+    return bytes(out[: n.value])
 
 
 def partition(prefix: np.ndarray, parts: int) -> np.ndarray:

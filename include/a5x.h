@@ -241,6 +241,41 @@ A5X_API int a5x_format_hits(a5x_ctx* ctx, const uint8_t* words, const uint64_t* 
                             int mode, int min, int max, const a5x_hit* hits, uint64_t n_hits, a5x_sink_fn sink,
                             void* user);
 
+/* ---- hashcat rules in the digest + lookup stage (no reference counterpart: the
+ * reference's pipeline hands its candidates to "hashcat ... -r best66.rule", README.MD:69,
+ * :163) ------------------------------------------------------------------------- */
+/* While a context holds >= 1 rule, every a5x_expand_digest* call hashes each candidate
+ * once per rule (the rule applied first) and a hit names (word, cand) and a rule; with no
+ * rules nothing changes.  The rule language is the hashcat subset of DESIGN.md "Rules":
+ * words of at most A5X_RULE_LMAX = 128 bytes at any point, at most 31 functions a rule. */
+/* Replace the context's rule set from rule-file text (NULL / 0: clear).  *n_rules =
+ * accepted, *n_skipped = lines skipped as unsupported or malformed.  Works on a
+ * host-only context (parse only). */
+A5X_API int a5x_set_rules(a5x_ctx* ctx, const uint8_t* text, size_t len, uint32_t* n_rules, uint32_t* n_skipped);
+A5X_API int a5x_load_rules_file(a5x_ctx* ctx, const char* path, uint32_t* n_rules, uint32_t* n_skipped);
+A5X_API int a5x_rule_count(const a5x_ctx* ctx);
+/* Latest a5x_expand_digest* call: the rule index of each hit copied to the caller, in hit
+ * order (rule_out == NULL: *n only); a5x_rules_last: hashes computed, and candidates
+ * rejected (hashed under no rule) as longer than A5X_RULE_LMAX.  a5x_digest_lines_rules_device
+ * sets the two counts too. */
+A5X_API int a5x_hit_rules(a5x_ctx* ctx, uint32_t* rule_out, uint64_t cap, uint64_t* n);
+A5X_API int a5x_rules_last(a5x_ctx* ctx, uint64_t* hashed, uint64_t* rejected);
+/* a5x_format_hits with the ruled plain, "hexdigest:rule(candidate)\n": the candidate is
+ * regenerated as there, then hit_rule[i] (n_hits entries, of the context's current rule
+ * set) is applied to it on the host with the interpreter the kernel runs. */
+A5X_API int a5x_format_hits_rules(a5x_ctx* ctx, const uint8_t* words, const uint64_t* word_off, uint64_t n_words,
+                                  int mode, int min, int max, const a5x_hit* hits, uint64_t n_hits,
+                                  const uint32_t* hit_rule, a5x_sink_fn sink, void* user);
+/* a5x_digest_lines_device under the context's R rules: the digest of (line i, rule r) at
+ * index i * R + r; a rejected line's R digests are all zero.  digests_cap counts digests
+ * (lines x R); d_digests 4-B aligned.  Verification hook. */
+A5X_API int a5x_digest_lines_rules_device(a5x_ctx* ctx, int algo, const uint8_t* d_lines, uint64_t nbytes,
+                                          uint8_t* d_digests, uint64_t digests_cap, uint64_t* n_lines, void* stream);
+/* Pure host: parse one rule line and apply it to word (len <= A5X_RULE_LMAX) with the
+ * a5x_rules.h interpreter.  A5X_E_ARG for a line a5x_set_rules would skip or ignore. */
+A5X_API int a5x_debug_apply_rule(const uint8_t* rule, size_t rule_len, const uint8_t* word, size_t len,
+                                 uint8_t* out, size_t cap, size_t* out_len);
+
 /* Output byte offset, in the batch's full "cand\n" stream, of each global candidate index
  * cands[i] (cands[i] = the batch's total candidates gives its total bytes; larger: clamped).
  * Device-resident words; the keyspace runs once per call.  Candidate numbering is the one
