@@ -2420,6 +2420,74 @@ int a5x_debug_plan_word(a5x_ctx* c, const uint8_t* word, size_t len, int mn, int
   return A5X_OK;
 }
 
+extern "C++" {
+template <u32 CAP>
+static void plan_sizes_rows(const GWord& gw, u32 L, const Tab& T, uint32_t* cnt, uint32_t* bld) {
+  std::vector<u64> rec(1 + 128 + 64 * FW_UMAXR + 128, 0);  // (np, ne of any word of <= 64 bytes)
+  ArraySink sk;
+  sk.rec = rec.data(); sk.np = 128;
+  CountPlanner<CAP> cp;
+  Planner<true, GWord, ArraySink, CAP> pb(gw, T, sk);
+  u32 p = 0;
+  Unit U;
+  while (next_unit(gw, L, p, T, U)) {
+    cp.unit(U);
+    pb.unit(U);
+  }
+  cp.finish(L);
+  pb.finish(L);
+  pb.pick_balanced();
+  const Plan* P[2] = {&cp.P, &pb.P};
+  uint32_t* o[2] = {cnt, bld};
+  for (int k = 0; k < 2; k++) {
+    const Plan& Q = *P[k];
+    const uint32_t v[8] = {Q.ok ? 1u : 0u, Q.np, Q.ng, Q.ne, Q.maxl, Q.minl, Q.nbig, Q.bent};
+    for (int j = 0; j < 8; j++) o[k][j] = v[j];
+  }
+}
+}  // extern "C++"
+
+int a5x_debug_plan_sizes(a5x_ctx* c, const uint8_t* word, size_t len, uint32_t* out) {
+  if (!c || !out || (!word && len)) return A5X_E_ARG;
+  if (len > A5X_LMAX_A) return fail(c, A5X_E_ARG, "word of %zu bytes (the planners take <= %d)", len, A5X_LMAX_A);
+  if (c->table.keys.empty()) return fail(c, A5X_E_NOTABLE, "no substitution table loaded");
+  if (c->table_dirty || c->blob.empty()) {
+    int rc = compile_table(c);
+    if (rc) return rc;
+  }
+  std::vector<uint8_t> wb(word, word + len);
+  wb.resize(len + 16, 0);
+  GWord gw;
+  gw.p = wb.data();
+  const Tab T = tab_view(c->blob.data());
+  const u32 L = (u32)len;
+  for (int j = 0; j < 40; j++) out[j] = 0;
+  plan_sizes_rows<FW_UMAXR>(gw, L, T, out, out + 8);
+  plan_sizes_rows<8>(gw, L, T, out + 16, out + 24);
+  // k_keyspace_cplx's two paths: the record planned from the units of the classification
+  // walk (cluster choices left in the sink by that walk) against plan_word's own walk
+  std::vector<u64> ra(FX_WREC + FW_PMAX + 16, 0), rb(FX_WREC + FW_PMAX + 16, 0);
+  ArraySink sa, sb;
+  UnitCache uc;
+  const WordClass C = classify_word(gw, L, T, 0, 15, A5X_RING_A - 16, &uc, sb.c, 1);
+  if (!(C.flags & A5X_WF_FAST) || (C.flags & A5X_WF_DEFER) || C.count == 0) {
+    out[32] = 3;
+    return A5X_OK;
+  }
+  if (uc.full) {
+    out[32] = 2;
+    return A5X_OK;
+  }
+  sa.rec = ra.data(); sa.np = ff_np(C.flags);
+  sb.rec = rb.data(); sb.np = ff_np(C.flags);
+  const Plan PA = plan_word<true>(gw, L, T, sa, fb_balanced_cap(C.count + 1));
+  const Plan PB = plan_word_cached(gw, L, T, sb, uc, fb_balanced_cap(C.count + 1));
+  ra[0] = fr_hdr(PA.np, PA.ng, PA.ne, PA.maxl, PA.nbig, PA.bstarts, PA.bRp);
+  rb[0] = fr_hdr(PB.np, PB.ng, PB.ne, PB.maxl, PB.nbig, PB.bstarts, PB.bRp);
+  out[32] = PA.ok && PB.ok && PA.minl == PB.minl && PA.bent == PB.bent && ra == rb ? 1u : 0u;
+  return A5X_OK;
+}
+
 int a5x_set_targets(a5x_ctx* c, int algo, const uint8_t* dig, uint64_t n) {
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || (n && !dig)) return A5X_E_ARG;

@@ -291,6 +291,13 @@ __device__ __forceinline__ u32 wave_append(bool pred, u32* ctr) {
                   // 2 no planner in the count pass, 4 no record stores
 #endif
 
+#ifndef KS_LEAN_COUNT
+#define KS_LEAN_COUNT 1  // k_keyspace_thread's count pass plans with CountPlanner (0: Planner<false>; A/B builds)
+#endif
+#ifndef KC_ONCE
+#define KC_ONCE 1        // k_keyspace_cplx walks a word once (ks_word_once; 0: ks_classify + ks_build; A/B builds)
+#endif
+
 // k_keyspace_thread's open group holds KS_GCAP entries (a unit with more choices
 // makes the word complex: k_keyspace_cplx plans it with FW_UMAXR)
 #define KS_GCAP 8
@@ -344,6 +351,40 @@ __device__ __forceinline__ void ks_build(const W& wd, u32 L, const Tab& T, const
   const Plan P = plan_word<true>(wd, L, T, sk, fb_balanced_cap(count + 1));
   rec[0] = fr_hdr(P.np, P.ng, P.ne, P.maxl, P.nbig, P.bstarts, P.bRp);
   if (!P.ok || P.ng != ff_ng(f) || P.ne != ff_ne(f) || P.np != ff_np(f)) atomicOr(a.err, A5X_DERR_STATE);
+}
+
+// k_keyspace_cplx: ks_classify + ks_build with one unit walk per word.  The walk keeps
+// its units (UnitCache) and enumerates every cluster once, with its choices left in the
+// cluster half of the lane's scratch (g + 256 FW_UMAXR, which classification does not
+// use otherwise); the build plans from the cache and re-enumerates only the clusters
+// whose choices a later cluster overwrote.  A word the cache cannot hold is built by
+// ks_build's second walk.
+template <class W>
+__device__ __forceinline__ u32 ks_word_once(const W& wd, u64 L64, const Tab& T, const KsArgs& a, WordClass& C, bool fits,
+                                            u64* rec, u64* g) {
+  if (L64 > A5X_LMAX_A && a.mx >= 1) return A5X_WF_DEFER;  // long words: the wave kernel
+  UnitCache uc;
+#if KC_ONCE
+  C = classify_word(wd, (u32)L64, T, a.mn, a.mx, A5X_RING_A - 16, &uc, g + 256 * FW_UMAXR, 256u);
+#else
+  C = classify_word(wd, (u32)L64, T, a.mn, a.mx, A5X_RING_A - 16);
+  uc.full = true;
+#endif
+  u32 f = C.flags;
+  if (C.ovf) atomicOr(a.err, A5X_DERR_OVF);
+  if ((f & A5X_WF_DEFER) || !(f & (A5X_WF_FAST | A5X_WF_RADIX | A5X_WF_ERR_OVF)))
+    f = A5X_WF_DEFER;  // capped windows, unit limits, non-FAST clusters: the DP kernel
+  if (!((f & A5X_WF_FAST) && C.count > 0 && fits)) return f;
+  if (uc.full) {
+    ks_build(wd, (u32)L64, T, a, f, C.count, rec, g);
+    return f;
+  }
+  DevRecSink sk;
+  sk.g = g; sk.c = g + 256 * FW_UMAXR; sk.rec = rec; sk.np = ff_np(f);
+  const Plan P = plan_word_cached(wd, (u32)L64, T, sk, uc, fb_balanced_cap(C.count + 1));
+  rec[0] = fr_hdr(P.np, P.ng, P.ne, P.maxl, P.nbig, P.bstarts, P.bRp);
+  if (!P.ok || P.ng != ff_ng(f) || P.ne != ff_ne(f) || P.np != ff_np(f)) atomicOr(a.err, A5X_DERR_STATE);
+  return f;
 }
 
 // Position-synchronous word walk of k_keyspace_thread: every lane steps through byte
@@ -506,8 +547,12 @@ __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
     // ---- pass 1: units -> counts + piece plan (count mode) ----
     CountAcc A;
     count_init(A, L);
+#if KS_LEAN_COUNT
+    CountPlanner<KS_GCAP> pl;
+#else
     NullSink ns;
     Planner<false, LWord, NullSink, KS_GCAP> pl(lw, T, ns);
+#endif
     u32 nlog = 0;
     const bool rm = a.rmode != 0;
     bool rep = false;  // (-s / -s -r with vocc: a repeated pattern; the occurrences logged)
@@ -1528,13 +1573,11 @@ __global__ void __launch_bounds__(256) k_keyspace_cplx(KsArgs a) {
       }
       LWord lw;
       lw.base = wst; lw.off = threadIdx.x * KC_SLOT;
-      f = ks_classify(lw, L64, T, a, C);
-      if ((f & A5X_WF_FAST) && C.count > 0 && fits) ks_build(lw, (u32)L64, T, a, f, C.count, rec, gbuf + threadIdx.x);
+      f = ks_word_once(lw, L64, T, a, C, fits, rec, gbuf + threadIdx.x);
     } else {
       GWord gw;
       gw.p = a.words + s;
-      f = ks_classify(gw, L64, T, a, C);
-      if ((f & A5X_WF_FAST) && C.count > 0 && fits) ks_build(gw, (u32)L64, T, a, f, C.count, rec, gbuf + threadIdx.x);
+      f = ks_word_once(gw, L64, T, a, C, fits, rec, gbuf + threadIdx.x);
     }
     if ((f & A5X_WF_FAST) && C.count > 0) {
       if (fits) a.roff[w] = (u32)(a.cplx_base + (u64)i * FW_RMAX);

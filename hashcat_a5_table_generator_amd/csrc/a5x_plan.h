@@ -274,8 +274,11 @@ A5X_HD void cluster_choices(const W& wd, Unit& U, const Tab& T, int target, u64*
 }
 
 // Next unit at or after p (p advances past it).  Returns false at the end of the word.
+// cbuf: a cluster's statistics come from the target -2 enumeration, which also leaves its
+// choices in cbuf[a * cstride] (k_keyspace_cplx: the build pass then needs no enumeration
+// of its own for that cluster); nullptr: statistics only.
 template <class W>
-A5X_HD bool next_unit(const W& wd, u32 L, u32& p, const Tab& T, Unit& U) {
+A5X_HD bool next_unit(const W& wd, u32 L, u32& p, const Tab& T, Unit& U, u64* cbuf = nullptr, u32 cstride = 1) {
   for (; p < L; p++) {
     u32 e = p, nmatch = 0, k0 = 0;
     U.m0 = 0; U.m1 = 0;
@@ -308,7 +311,7 @@ A5X_HD bool next_unit(const W& wd, u32 L, u32& p, const Tab& T, Unit& U) {
       U.ok = true;
     } else {
       U.key = ~0u; U.k = nmatch;
-      if (U.ok) cluster_choices(wd, U, T, -1, nullptr, nullptr);
+      if (U.ok) cluster_choices(wd, U, T, cbuf ? -2 : -1, cbuf, nullptr, cstride);
     }
     p = e;
     return true;
@@ -461,7 +464,8 @@ struct Planner {
     big_add(1, n, P.np);
     P.ne++; P.np++; P.lconst += n; P.maxl += n; P.minl += n;
   }
-  A5X_HD void unit(const Unit& U) {
+  // have_choices: the cluster's choices are already in the sink's cbuf (next_unit with cbuf)
+  A5X_HD void unit(const Unit& U, bool have_choices = false) {
     if (!P.ok) return;
     const u32 Ru = U.R, ml = U.ml, run = U.s - prev;
     if (!U.ok || ml > FW_PLEN || Ru > CAP || Ru < 2) { P.ok = false; return; }
@@ -470,8 +474,10 @@ struct Planner {
     if constexpr (BUILD) {
       if (U.k) {  // cluster: all choices once (unit_choice would re-enumerate per entry)
         cb = sk.cbuf(); cs = sk.cstride();
-        Unit V = U;
-        cluster_choices(wd, V, T, -2, cb, nullptr, cs);
+        if (!have_choices) {
+          Unit V = U;
+          cluster_choices(wd, V, T, -2, cb, nullptr, cs);
+        }
       }
     }
     if (open && cmax + run + ml <= FW_PLEN && cR * Ru <= CAP) {
@@ -578,12 +584,184 @@ struct Planner {
   }
 };
 
+// The count pass of k_keyspace_thread: Planner<false> reduced to what the class decision
+// (classify_finish: ok, np, ne, maxl, minl, nbig, bent) and the FAST flag fields (np, ng,
+// ne) read.  No piece starts, literal bytes, big-piece starts or packed R, no balanced
+// grouping; a run of literal pieces is accounted in closed form (nothing is stored per
+// literal).  Same cuts as Planner: a5x_debug_plan_sizes / tests/test_plan_count_mode.py
+// compare the two, and the build pass checks np / ng / ne against it per word.
+template <u32 CAP = FW_UMAXR>
+struct CountPlanner {
+  static_assert(2 * FW_PLEN <= FB_PLEN && 3 * FW_PLEN > FB_PLEN && FB_SPAN >= 3 && FB_RMAX >= 1,
+                "lit_full: two full literal pieces fill a big piece");
+  // The two flags of the walk are kept as numbers, not bools: a bool that lives across the
+  // divergent branches of the position loop is a lane mask that every join has to merge.
+  Plan P;             // lconst, bstarts, bRp stay 0; ok is set by finish()
+  u32 refused;        // units that do not fit a piece (Planner: P.ok = false)
+  u32 bR, bl, bspan;  // the big piece being filled
+  u32 cR, cmax, cmin, prev;  // cR = 0: no open group
+
+  A5X_HD CountPlanner() {
+    P.np = 0; P.ng = 0; P.ne = 0; P.lconst = 0; P.maxl = 0; P.minl = 0; P.ok = true;
+    P.nbig = 0; P.bstarts = 0; P.bent = 0; P.bRp = 0;
+    refused = 0; bR = 1; bl = 0; bspan = 0; cR = 0; cmax = 0; cmin = 0; prev = 0;
+  }
+  // Planner::big_join without the header fields, for a small piece that exists when c
+  A5X_HD void big(u32 R, u32 maxlen, bool c = true) {
+    const bool join = P.nbig && bl + maxlen <= FB_PLEN && bR * R <= FB_RMAX && bspan < FB_SPAN;
+    const u32 nR = join ? bR * R : R;
+    P.bent += c ? (join ? nR - bR : R) : 0u;
+    P.nbig += c && !join ? 1u : 0u;
+    bR = c ? nR : bR; bl = c ? (join ? bl + maxlen : maxlen) : bl; bspan = c ? (join ? bspan + 1u : 1u) : bspan;
+  }
+  // m literal pieces of FW_PLEN bytes (R = 1).  At most two join the open big piece (the
+  // second needs bl <= FB_PLEN - 2 FW_PLEN before the first); the rest open big pieces in
+  // pairs: FW_PLEN, 2 FW_PLEN <= FB_PLEN < 3 FW_PLEN.
+  A5X_HD void lit_full(u32 m) {
+#pragma unroll
+    for (u32 t = 0; t < 2; t++) {
+      const bool j = m && P.nbig && bl + FW_PLEN <= FB_PLEN && bR <= FB_RMAX && bspan < FB_SPAN;
+      bl += j ? FW_PLEN : 0u; bspan += j ? 1u : 0u; m -= j ? 1u : 0u;
+    }
+    const u32 nb = (m + 1u) >> 1;
+    P.nbig += nb; P.bent += nb;
+    bR = m ? 1u : bR;
+    bl = m ? ((m & 1u) ? FW_PLEN : 2u * FW_PLEN) : bl;
+    bspan = m ? 2u - (m & 1u) : bspan;
+  }
+  // the literal pieces of Planner's splitting loops: m full ones, then one of r bytes (r > 0)
+  A5X_HD void lits(u32 m, u32 r) {
+    const u32 k = m + (r ? 1u : 0u), nb = m * FW_PLEN + r;
+    P.np += k; P.ne += k; P.maxl += nb; P.minl += nb;
+    lit_full(m);
+    big(1, r, r != 0);
+  }
+  A5X_HD void close_group(bool c = true) {
+    big(cR, cmax, c);
+    P.ne += c ? cR : 0u; P.ng += c ? 1u : 0u; P.maxl += c ? cmax : 0u; P.minl += c ? cmin : 0u;
+    cR = c ? 0u : cR;
+  }
+  // Straight-line (selects, no branches): the lanes of a wave are at different units, so a
+  // branchy version runs every path anyway and pays for merging the lane masks of its
+  // flags at every join.  After a refused unit the other fields are not meaningful (Planner
+  // stops there; nothing reads them).
+  A5X_HD void unit(const Unit& U) {
+    const u32 Ru = U.R, ml = U.ml, run = U.s - prev;
+    refused += U.ok && ml <= FW_PLEN && Ru <= CAP && Ru >= 2 ? 0u : 1u;
+    const bool open = cR != 0, merge = open && cmax + run + ml <= FW_PLEN && cR * Ru <= CAP;
+    close_group(open && !merge);
+    // Planner: while (rem + ml > FW_PLEN) literal(min(FW_PLEN, rem)) -- full pieces while
+    // rem >= FW_PLEN (ml = 0: while rem > FW_PLEN), then the rest when it does not fit with
+    // the unit (then rest > 0, as ml <= FW_PLEN)
+    const bool split = !merge && run + ml > FW_PLEN;
+    const u32 m = split ? (run - (ml ? 0u : 1u)) / FW_PLEN : 0u, rest = run - m * FW_PLEN;
+    const bool part = split && rest + ml > FW_PLEN;
+    lits(m, part ? rest : 0u);
+    const u32 rem = part ? 0u : rest;
+    cR = merge ? cR * Ru : Ru;
+    cmax = merge ? cmax + run + ml : rem + ml;
+    cmin = merge ? cmin + run + U.mnl : rem + U.mnl;
+    P.np += merge ? 0u : 1u;
+    prev = U.e;
+  }
+  A5X_HD void finish(u32 L) {  // tail bytes + '\n'
+    P.ok = refused == 0;
+    if (!P.ok) return;
+    const u32 tl = L - prev + 1;
+    if (cR && cmax + tl <= FW_PLEN) {
+      cmax += tl; cmin += tl;
+      close_group();
+    } else {
+      if (cR) close_group();
+      lits(tl / FW_PLEN, tl % FW_PLEN);
+    }
+  }
+};
+
 template <bool BUILD, class W, class S>
 A5X_HD Plan plan_word(const W& wd, u32 L, const Tab& T, S& sk, u32 balanced_cap = 0) {
   Planner<BUILD, W, S> pl(wd, T, sk, balanced_cap);
   u32 p = 0;
   Unit U;
   while (pl.P.ok && next_unit(wd, L, p, T, U)) pl.unit(U);
+  pl.finish(L);
+  pl.pick_balanced();
+  return pl.P;
+}
+
+// The units of one next_unit walk, kept so that the build pass of k_keyspace_cplx does
+// not walk the word again.  Per lane, in registers (the kernel's LDS is at its
+// residency limit; at 2 waves per SIMD it has registers to spare): UC_UNITS units of 16
+// bits, s << 10 | key for a lone match (lone_unit rebuilds the rest), s << 10 | UC_CL for
+// a cluster, whose matches and cluster_choices statistics are kept for the first
+// UC_CLUSTERS clusters.  A word that does not fit (full) takes the two-walk path.
+#define UC_UNITS 8
+#define UC_CLUSTERS 2
+#define UC_CL 1023u
+A5X_HD void lone_unit(const Tab& T, u32 s, u32 k, Unit& U);
+struct UnitCache {
+  u64 ul0, ul1;                // units 0-3 / 4-7
+  u64 m0[UC_CLUSTERS], m1[UC_CLUSTERS];
+  u64 st[UC_CLUSTERS];         // span | k << 8 | R << 12 | ml << 20 | mnl << 24 | spos << 28 | sneg << 36 | (maxd + 128) << 48
+  u32 n, nc;
+  u32 res;                     // the unit whose choices the cluster buffer holds (~0u: none)
+  bool full;
+  A5X_HD UnitCache() {
+    ul0 = 0; ul1 = 0; n = 0; nc = 0; res = ~0u; full = false;
+    for (u32 j = 0; j < UC_CLUSTERS; j++) { m0[j] = 0; m1[j] = 0; st[j] = 0; }
+  }
+  A5X_HD void push(const Unit& U, bool enumerated) {
+    if (full) return;
+    const u32 span = U.e - U.s;
+    // (an ok cluster: R <= FW_UMAXR choices of <= FW_PLEN bytes, <= FW_UMAXM matches)
+    const bool fits = n < UC_UNITS && U.s < 64u && U.ok &&
+                      (U.k ? nc < UC_CLUSTERS && span < 128u && U.spos < 256u && U.sneg < 4096u : U.key < UC_CL);
+    if (!fits) { full = true; return; }
+    const u64 f = (u64)((U.s << 10) | (U.k ? UC_CL : U.key)) << (16 * (n & 3u));
+    if (n < 4) ul0 |= f; else ul1 |= f;
+    if (U.k) {
+      const u64 s = (u64)span | ((u64)U.k << 8) | ((u64)U.R << 12) | ((u64)U.ml << 20) | ((u64)U.mnl << 24) |
+                    ((u64)U.spos << 28) | ((u64)U.sneg << 36) | ((u64)(u32)(U.maxd + 128) << 48);
+#pragma unroll
+      for (u32 j = 0; j < UC_CLUSTERS; j++)
+        if (j == nc) { m0[j] = U.m0; m1[j] = U.m1; st[j] = s; }
+      nc++;
+      if (enumerated) res = n;
+    }
+    n++;
+  }
+  // unit i (in order, i = 0 .. n - 1; ci = the clusters before it, advanced here)
+  A5X_HD void get(const Tab& T, u32 i, u32& ci, Unit& U) const {
+    const u32 e = (u32)((i < 4 ? ul0 : ul1) >> (16 * (i & 3u))) & 0xFFFFu;
+    const u32 s = e >> 10, key = e & 1023u;
+    if (key != UC_CL) { lone_unit(T, s, key, U); return; }
+    u64 a = 0, b = 0, c = 0;
+#pragma unroll
+    for (u32 j = 0; j < UC_CLUSTERS; j++)
+      if (j == ci) { a = m0[j]; b = m1[j]; c = st[j]; }
+    ci++;
+    U.s = s; U.e = s + ((u32)c & 255u);
+    U.k = (u32)(c >> 8) & 15u; U.nm = U.k; U.key = ~0u; U.cb = 0;
+    U.R = (u32)(c >> 12) & 255u; U.ml = (u32)(c >> 20) & 15u; U.mnl = (u32)(c >> 24) & 15u;
+    U.spos = (u32)(c >> 28) & 255u; U.sneg = (u32)(c >> 36) & 4095u; U.maxd = (int)((u32)(c >> 48) & 255u) - 128;
+    U.m0 = a; U.m1 = b; U.ok = true;
+  }
+};
+
+// plan_word<true> from the cached units of a walk (uc.full: not for this word).  A cluster
+// whose choices the walk left in the sink's cbuf (uc.res) is not enumerated again; any
+// other cluster's enumeration overwrites that buffer.
+template <class W, class S>
+A5X_HD Plan plan_word_cached(const W& wd, u32 L, const Tab& T, S& sk, const UnitCache& uc, u32 balanced_cap = 0) {
+  Planner<true, W, S> pl(wd, T, sk, balanced_cap);
+  u32 ci = 0, res = uc.res;
+  for (u32 i = 0; i < uc.n && pl.P.ok; i++) {
+    Unit U;
+    uc.get(T, i, ci, U);
+    const bool have = U.k && i == res;
+    if (U.k && !have) res = ~0u;
+    pl.unit(U, have);
+  }
   pl.finish(L);
   pl.pick_balanced();
   return pl.P;
@@ -699,9 +877,11 @@ A5X_HD WordClass classify_finish(const CountAcc& A, const Plan& PL, u32 L, int m
   return C;
 }
 
-// One walk over the units: counts and the piece plan (count mode) together.
+// One walk over the units: counts and the piece plan (count mode) together.  uc: the
+// units are kept for plan_word_cached; cbuf: see next_unit.
 template <class W>
-A5X_HD WordClass classify_word(const W& wd, u32 L, const Tab& T, int mn, int mx, u32 ringmax) {
+A5X_HD WordClass classify_word(const W& wd, u32 L, const Tab& T, int mn, int mx, u32 ringmax, UnitCache* uc = nullptr,
+                               u64* cbuf = nullptr, u32 cstride = 1) {
   if (mx < 1 || L == 0) {  // processWord emits nothing
     WordClass C;
     C.count = 0; C.bytes = 0; C.ovf = false; C.clusters = false;
@@ -714,10 +894,11 @@ A5X_HD WordClass classify_word(const W& wd, u32 L, const Tab& T, int mn, int mx,
   Planner<false, W, NullSink> pl(wd, T, ns);
   u32 p = 0;
   Unit U;
-  while (next_unit(wd, L, p, T, U)) {
+  while (next_unit(wd, L, p, T, U, cbuf, cstride)) {
     count_unit(A, U);
     if (!A.ok) break;
     pl.unit(U);
+    if (uc) uc->push(U, cbuf != nullptr);
   }
   pl.finish(L);
   return classify_finish(A, pl.P, L, mn, mx, ringmax);

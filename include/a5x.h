@@ -313,6 +313,15 @@ A5X_API int a5x_debug_stamps(unsigned long long* out16, int reset);
 A5X_API int a5x_debug_plan_word(a5x_ctx* ctx, const uint8_t* word, size_t len, int min_sub, int max_sub,
                                 uint8_t* out, size_t cap, uint64_t* info);
 
+/* Test hook (CPU test suite): the piece-plan sizes of ONE word (<= 64 bytes) from the
+ * count-mode planner of the keyspace count pass and from the build-mode planner, which
+ * must agree.  out[40]: rows of 8 = {ok, np, ng, ne, maxl, minl, nbig, bent} (past ok = 0:
+ * unspecified): row 0 count mode / row 1 build mode with groups of <= 16 entries, rows 2 / 3
+ * the same with groups of <= 8; out[32] = the record built from the cached units of one
+ * walk (k_keyspace_cplx) against the two-walk record: 1 equal, 0 different, 2 the word does
+ * not fit the unit cache, 3 not a FAST word (no record); out[33..39] = 0. */
+A5X_API int a5x_debug_plan_sizes(a5x_ctx* ctx, const uint8_t* word, size_t len, uint32_t* out);
+
 /* Test hook (CPU test suite): the digest of msg[0, len) computed on the host by the
  * __host__ __device__ core the digest kernels run (a5x_sha.h; SHA-1 and SHA-256 only),
  * a5x_digest_size(algo) bytes into out.  Never called by a compute path. */
