@@ -1325,13 +1325,9 @@ void build_target_set(uint32_t W, const uint8_t* dig, uint64_t n, TargetSet& T) 
       continue;
     }
     const uint32_t bi = d[0] & (uint32_t)((1ull << bm_log2) - 1);
-    if (MD_BLOOM2) {  // (a5x_md.h md_prefilter: the 64-bit word of bi, two bits from word 3)
-      const uint64_t m = md_bloom_bits(d[3]);
-      bm[(bi >> 6) * 2] |= (uint32_t)m;
-      bm[(bi >> 6) * 2 + 1] |= (uint32_t)(m >> 32);
-    } else {
-      bm[bi >> 5] |= 1u << (bi & 31);
-    }
+    const uint64_t m = md_bloom_bits(d[3]);  // (a5x_md.h md_prefilter: the 64-bit word of bi, two bits from word 3)
+    bm[(bi >> 6) * 2] |= (uint32_t)m;
+    bm[(bi >> 6) * 2 + 1] |= (uint32_t)(m >> 32);
     for (uint64_t slot = tgt_slot(d, tmask);; slot = (slot + 1) & tmask) {
       uint4& e = tab[slot];
       if (e.x == d[0] && e.y == d[1] && e.z == d[2] && e.w == d[3] &&

@@ -105,25 +105,19 @@ __device__ __forceinline__ uint32_t lds4(const uint8_t* base, uint32_t off) {
 // Bloom filter: digest word 0 picks a 64-bit word, word 3 two bits in it (one load, both
 // bits tested): at 64 bits per target a false positive is ~1/1000 instead of 1/64, so a
 // wave of 64 candidates reaches the table probe in ~6 % of its rounds instead of ~63 %
-// (MD_BLOOM2=0: one bit, the round-4 filter; the host builds the same layout).  Words 0
-// and 3 are final two MD5 steps (MD4: two steps) before the end of the last block, so a
-// wave whose candidates all miss the filter skips those steps (md_block_probe).
-#ifndef MD_BLOOM2
-#define MD_BLOOM2 1
-#endif
+// (the host builds the same layout).  Words 0 and 3 are final two MD5 steps (MD4: two
+// steps) before the end of the last block, so a wave whose candidates all miss the filter
+// skips those steps (md_block_probe).
 __host__ __device__ __forceinline__ uint64_t md_bloom_bits(uint32_t d3) {
-  return MD_BLOOM2 ? (1ull << (d3 & 63u)) | (1ull << ((d3 >> 6) & 63u)) : 0ull;
+  return (1ull << (d3 & 63u)) | (1ull << ((d3 >> 6) & 63u));
 }
 // the prefilter alone, on digest words 0 and 3 (a possible all-zero target passes)
 __device__ __forceinline__ bool md_prefilter(const uint32_t* bitmap, uint32_t bm_mask, bool has_zero, uint32_t d0,
                                              uint32_t d3) {
   if (has_zero && (d0 | d3) == 0u) return true;
   const uint32_t bi = d0 & bm_mask;
-  if (MD_BLOOM2) {
-    const uint64_t m = md_bloom_bits(d3);
-    return (((const uint64_t*)bitmap)[bi >> 6] & m) == m;
-  }
-  return (bitmap[bi >> 5] >> (bi & 31u)) & 1u;
+  const uint64_t m = md_bloom_bits(d3);
+  return (((const uint64_t*)bitmap)[bi >> 6] & m) == m;
 }
 __device__ __forceinline__ bool md_probe(const uint32_t* bitmap, uint32_t bm_mask, const uint4* table, uint64_t tmask,
                                          bool has_zero, const uint32_t* d) {

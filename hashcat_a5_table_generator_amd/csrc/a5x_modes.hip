@@ -98,9 +98,6 @@ constexpr u32 MP_RING = 16 + 64 * A5X_M_CBUF + 48;
 #ifndef MF_NE2
 #define MF_NE2 128
 #endif
-#ifndef M_PREFETCH
-#define M_PREFETCH 1         // m_items: the next item's metadata and word bytes loaded under the current item
-#endif
 #ifndef MF_TCAP
 #define MF_TCAP 48           // tokens (and so pieces) per word in the piece layout; more: the token ring
 #endif
@@ -109,9 +106,6 @@ constexpr u32 MP_RING = 16 + 64 * A5X_M_CBUF + 48;
 #endif
 #ifndef MF_K
 #define MF_K 2               // leaves per lane run (odometer steps between them; C5: 2 < 4 < 8)
-#endif
-#ifndef MF_OFF
-#define MF_OFF 0             // 1: radix words stay on the token ring (A/B builds)
 #endif
 #ifndef MF_ABL
 #define MF_ABL 0             // timing ablations (diagnostic builds): 1 = no expansion, 2 = no pieces, 4 = no tokens
@@ -1517,7 +1511,7 @@ __device__ __forceinline__ void m_count_word(SL& S, const MT& T, const A5xModeLa
       const u32 ntok = m_pos_setup(S, T, I, a.mode);
       if (ntok && a.mode == A5X_MODE_REVERSE) wb = I.count * (u64)(I.L + 1);
       else if (ntok && S.radix) wb = m_pos_prefix(S, I, I.count) - m_pos_prefix(S, I, 0);
-      if (wb != ~0ull && I.radix && !MF_OFF && ntok <= MF_TCAP)
+      if (wb != ~0ull && I.radix && ntok <= MF_TCAP)
         wb |= S.nent <= MF_NE ? M_WB_FAST : S.nent <= MF_NE2 ? M_WB_FAST2 : 0ull;
     }
     if (m_lane() == 0) a.wbytes[w] = wb;
@@ -1625,7 +1619,7 @@ __global__ void __launch_bounds__(256) k_mode_count_thread(A5xModeLaunch a) {
       // m_pos_setup's table limits (entries of the patterns, then the literal chunks)
       const bool pos = L <= A5X_M_LMAX && npe <= MP_NE && npe + nlit <= MP_NE;
       if (pos && count > 0 && count <= a.SEG)
-        wb = bytes | (MF_OFF || nocc + nlit > MF_TCAP ? 0ull
+        wb = bytes | (nocc + nlit > MF_TCAP ? 0ull
                       : npe + nlit <= MF_NE ? M_WB_FAST : npe + nlit <= MF_NE2 ? M_WB_FAST2 : 0ull);
       a.count[w] = count;
       a.nseg[w] = (count + a.SEG - 1) / a.SEG;
@@ -1782,7 +1776,7 @@ __device__ void m_item(SL& S, const MT& T, const A5xModeLaunch& a, u64 i, int op
       return;
     }
     if (m_lane() == 0)
-      a.item_fl[i] = ntok ? (I.radix && !MF_OFF && ntok <= MF_TCAP && S.nent <= MF_NE2
+      a.item_fl[i] = ntok ? (I.radix && ntok <= MF_TCAP && S.nent <= MF_NE2
                                  ? (S.nent <= MF_NE ? MI_FAST : MI_FAST2) : MI_POS)
                           : a.mode == A5X_MODE_REVERSE ? MI_BUILD : MI_BUILD_LEN;
     if (!ntok && a.mode != A5X_MODE_REVERSE) return;  // lengths need the byte builder
@@ -1858,10 +1852,6 @@ __device__ __forceinline__ void m_items(const A5xModeLaunch& a, int op, uint8_t 
       P.b0 = (L <= A5X_M_LMAX && lane < L) ? a.words[P.w0 + lane] : 0u;
       P.b1 = (L <= A5X_M_LMAX && lane + 64 < L) ? a.words[P.w0 + lane + 64] : 0u;
     };
-    if (!M_PREFETCH) {
-      for (; m; m &= m - 1) m_item(S, T, a, b0 + (u64)__builtin_ctzll(m), op);
-      continue;
-    }
     MPre cur;
     if (m) meta((u32)__builtin_ctzll(m), cur);
     while (m) {

@@ -4,8 +4,9 @@ ds_*_b64 in four 16-lane groups; one cycle per extra address on a bank).
 
 Rounds of 64 lanes x K=4 candidates, each candidate split into NB equal pieces (the plan's
 big pieces), every piece OR-placed with wave-uniform dword counts (a5x_ring.h fx7_put).
-Strategies: piece (the kernel), piece_swz (XOR-swizzled ring, FX_SWZ), piece_mask (exec-masked
-ORs), piece_b64 (ds_or_b64), cand (whole candidates assembled in VGPRs), run (whole runs).
+Strategies: piece (the kernel), piece_swz (XOR-swizzled ring: a kernel variant that was
+measured, rejected and removed), piece_mask (exec-masked ORs), piece_b64
+(ds_or_b64), cand (whole candidates assembled in VGPRs), run (whole runs).
 
     python tools/bank_sim.py [workload] [words] [NB]
 """
