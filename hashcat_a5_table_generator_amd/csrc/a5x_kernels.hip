@@ -1591,6 +1591,7 @@ struct WaveLds {
 struct WordInfo {
   u32 L, nmatch, nslots;
   u32 cls;         // A5X_WF_RADIX [| A5X_WF_BIN] or A5X_WF_GENERAL; 0 = no candidates
+  u32 wide;        // radix word of more than 2^32 combinations: 64-bit digits (slot_digit)
   u32 fits;        // 1: the word's setup fit this pass's LDS budget
   u32 freew, W, Cc;
   int lo;
@@ -1618,7 +1619,7 @@ __device__ WordInfo wave_setup(WaveLds<LMAX, MLMAX, DPENT>& S, const Tab& T, con
   const u64 s = woff[w];
   const u64 L64 = woff[w + 1] - s;
   I.L = (u32)min(L64, (u64)0xffffffffu);
-  I.cls = 0; I.fits = 1; I.nslots = 0; I.count = 0; I.bytes = 0; I.ovf = 0; I.nev = 0;
+  I.cls = 0; I.wide = 0; I.fits = 1; I.nslots = 0; I.count = 0; I.bytes = 0; I.ovf = 0; I.nev = 0;
   I.maxlen = 0; I.udelta = INT32_MIN; I.freew = 1; I.W = 2; I.Cc = 1; I.lo = 1; I.nmatch = 0; I.why = 0;
   if (mx < 1 || L64 == 0) return I;
   const u32 L = I.L;
@@ -1742,8 +1743,32 @@ __device__ WordInfo wave_setup(WaveLds<LMAX, MLMAX, DPENT>& S, const Tab& T, con
       I.udelta = bin ? ud : INT32_MIN;
       return I;
     }
+    if (!ovf) {
+      // 2^32 < P < 2^64: the same slots and the same numbering with 64-bit digits.  Bytes =
+      // (P - 1)(L + 1) + sum over slots of (P / R) (sum of the values' length deltas), split by
+      // sign and overflow-checked (serial: only such words get here, nslots is small)
+      bool o2 = false;
+      u64 Dp = 0, Dn = 0;
+      for (u32 i = 0; i < m; i++) {
+        const A5xKey key = T.keys[S.mlist[S.evm[i] >> 8]];
+        const u64 per = P / S.slots[i].R;
+        Dp = add_ovf(Dp, mul_ovf(per, (u64)key.sum_dpos, o2), o2);
+        Dn = add_ovf(Dn, mul_ovf(per, (u64)key.sum_dneg, o2), o2);
+      }
+      u64 byt = add_ovf(mul_ovf(P - 1, (u64)L + 1, o2), Dp, o2);
+      if (byt < Dn) o2 = true;
+      byt -= Dn;
+      if (byt >> 63) o2 = true;  // (radix_prefix_bytes sums signed 64-bit parts)
+      I.cls = A5X_WF_RADIX | (bin ? A5X_WF_BIN : 0u);
+      I.wide = 1;
+      I.count = P - 1;
+      I.bytes = byt;
+      I.ovf = o2 ? 1u : 0u;
+      I.udelta = bin ? ud : INT32_MIN;
+      return I;
+    }
     I.nslots = 0;
-    // overflowing radix words go through the DP (same counts, u64 walk)
+    // radix words whose P overflows 64 bits go through the DP (it reports the overflow)
   }
   // ---- general: DP over events with a count window ----
   // G[e][c]: completions from event e having made c substitutions (c clamped to 1 in
@@ -2158,6 +2183,23 @@ __device__ __forceinline__ void run_open(Run& R, u64 pos) {
   R.open = true;
 }
 
+// digit of slot sl of the candidate index n (n becomes the quotient): u32 n by the slot's
+// magic division, u64 n (words of more than 2^32 combinations) by a 64-bit division
+template <class N>
+__device__ __forceinline__ u32 slot_digit(N& n, const Slot& sl) {
+  if constexpr (sizeof(N) == 4) {
+    const u32 q = fastdiv(n, sl.magic, sl.shift);
+    const u32 d = n - q * sl.R;
+    n = q;
+    return d;
+  } else {
+    const u64 q = n / sl.R;
+    const u32 d = (u32)(n - q * sl.R);
+    n = q;
+    return d;
+  }
+}
+
 // prefix bytes of candidates [0, r) of a radix word (candidate r <-> idx r+1)
 template <int LMAX, int MLMAX, int DPENT>
 __device__ u64 radix_prefix_bytes(const WaveLds<LMAX, MLMAX, DPENT>& S, const Tab& T, const WordInfo& I, u64 r) {
@@ -2293,30 +2335,21 @@ __device__ bool expand_word(WaveLds<LMAX, MLMAX, DPENT>& S, u32* ring, const Tab
     u32 len = 0;
     Emit e;
     if (I.cls & A5X_WF_RADIX) {
-      const u32 idx = (u32)(rk + 1);
-      if (act) {
+      // candidate rk <-> index rk + 1 in the slots' mixed radix, slot 0 least significant
+      auto rlen = [&](auto n) {
         int l = (int)I.L + 1;
-        u32 n = idx;
         for (u32 i = 0; i < I.nslots; i++) {
           const Slot& sl = S.slots[i];
-          const u32 q = fastdiv(n, sl.magic, sl.shift);
-          const u32 d = n - q * sl.R;
-          n = q;
+          const u32 d = slot_digit(n, sl);
           if (d) l += (int)T.ch[sl.choice_base + d].len - (int)sl.klen;
         }
-        len = (u32)l;
-      }
-      const u32 incl = wave_incl_scan_u32(len);
-      const u32 tot = lane63(incl);
-      const u64 off = R.pos + incl - len - R.base;
-      if (act) {
-        e.acc = 0; e.n = (u32)off & 3u; e.dw = (u32)(off >> 2);
-        u32 prev = 0, n = idx;
+        return (u32)l;
+      };
+      auto remit = [&](auto n) {
+        u32 prev = 0;
         for (u32 i = 0; i < I.nslots; i++) {
           const Slot& sl = S.slots[i];
-          const u32 q = fastdiv(n, sl.magic, sl.shift);
-          const u32 d = n - q * sl.R;
-          n = q;
+          const u32 d = slot_digit(n, sl);
           if (sl.pos > prev) em_bytes<RING>(e, ring, S.wbuf, prev, sl.pos - prev);
           em_choice<RING>(e, ring, T, sl.choice_base + d);
           prev = sl.pos + sl.klen;
@@ -2324,6 +2357,14 @@ __device__ bool expand_word(WaveLds<LMAX, MLMAX, DPENT>& S, u32* ring, const Tab
         if (I.L > prev) em_bytes<RING>(e, ring, S.wbuf, prev, I.L - prev);
         em_put<RING>(e, ring, '\n', 1);
         em_finish<RING>(e, ring);
+      };
+      if (act) len = I.wide ? rlen((u64)(rk + 1)) : rlen((u32)(rk + 1));
+      const u32 incl = wave_incl_scan_u32(len);
+      const u32 tot = lane63(incl);
+      const u64 off = R.pos + incl - len - R.base;
+      if (act) {
+        e.acc = 0; e.n = (u32)off & 3u; e.dw = (u32)(off >> 2);
+        if (I.wide) remit((u64)(rk + 1)); else remit((u32)(rk + 1));
       }
       R.pos += tot;
     } else {
