@@ -6,11 +6,11 @@
 //
 //   a5x_generator <dict-file> -t <table> [-t <table> ...] [-m N] [-x N]
 //                 [--threads N] [-s] [-r] [--device N]
-//                 [--hashes <file> [--algo md5|ntlm|sha1|sha256] [--rules <file>]]
+//                 [--hashes <file> [--algo md5|ntlm|sha1|sha224|sha256|sha384|sha512] [--rules <file>]]
 //                 [--skip N] [--limit N] [--keyspace]
 //
 // --hashes (a5x extension): instead of printing the candidates for a
-// hashcat pipe (README.MD:69), hash them on the GPU (MD5 / NTLM / SHA-1 / SHA-256 + lookup) against
+// hashcat pipe (README.MD:69), hash them on the GPU (MD5 / NTLM / SHA-1 / SHA-2 + lookup) against
 // the hex digests of <file> and print what hashcat would report, "hash:plain" (plains
 // that hashcat would hexify as $HEX[...]), each target once, at its first candidate in
 // stream order (README.MD:74-106, :168).
@@ -59,7 +59,8 @@ static void usage(FILE* f) {
           "      --rules=FILE                  With --hashes: apply every hashcat rule of FILE to each candidate\n"
           "                                    before hashing (hashcat -r; long form only: -r is --reverse-sub)\n"
           "      --algo=md5                    Digest of --hashes: md5 (hashcat -m 0), ntlm (-m 1000),\n"
-          "                                    sha1 (-m 100) or sha256 (-m 1400)\n"
+          "                                    sha1 (-m 100), sha224 (-m 1300), sha256 (-m 1400),\n"
+          "                                    sha384 (-m 10800) or sha512 (-m 1700); a name or the -m number\n"
           "      --skip=0                      Resume: start at candidate N of the stream (a5x extension)\n"
           "      --limit=N                     Print at most N candidates (a5x extension)\n"
           "      --keyspace                    Print the number of candidates and exit (a5x extension)\n");
@@ -176,8 +177,8 @@ static int hexv(int c) {
   return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
 }
 
-// target digests: one hex digest per line (2 * a5x_digest_size(algo) hex digits: 32, 40
-// or 64; anything after them, e.g. a
+// target digests: one hex digest per line (2 * a5x_digest_size(algo) hex digits: 32 to
+// 128; anything after them, e.g. a
 // ":plain" of a potfile line, is ignored); other lines are counted and skipped.  Whole
 // lines of any length (getline): a long potfile plain is one line, never a continuation
 // piece read as a target.
@@ -190,11 +191,11 @@ static int load_targets(a5x_ctx* ctx, const char* path, int algo) {
   ssize_t n;
   uint64_t bad = 0;
   const int dsz = a5x_digest_size(algo);
-  if (dsz <= 0 || dsz > 32) { fclose(f); return a5x_set_targets(ctx, algo, nullptr, 0); }  // (reports the bad algorithm)
+  if (dsz <= 0 || dsz > 64) { fclose(f); return a5x_set_targets(ctx, algo, nullptr, 0); }  // (reports the bad algorithm)
   const size_t nhex = 2 * (size_t)dsz;
   while ((n = getline(&line, &cap, f)) >= 0) {
     size_t k = 0;
-    uint8_t d[32];
+    uint8_t d[64];
     for (; k < nhex && k < (size_t)n; k++) {
       const int v = hexv((unsigned char)line[k]);
       if (v < 0) break;
@@ -343,7 +344,13 @@ int main(int argc, char** argv) {
       else if (v == "ntlm" || v == "1000") algo = A5X_ALGO_NTLM;
       else if (v == "sha1" || v == "100") algo = A5X_ALGO_SHA1;
       else if (v == "sha256" || v == "1400") algo = A5X_ALGO_SHA256;
-      else { fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1 or sha256\n"); return 80; }
+      else if (v == "sha224" || v == "1300") algo = A5X_ALGO_SHA224;
+      else if (v == "sha384" || v == "10800") algo = A5X_ALGO_SHA384;
+      else if (v == "sha512" || v == "1700") algo = A5X_ALGO_SHA512;
+      else {
+        fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1, sha224, sha256, sha384 or sha512\n");
+        return 80;
+      }
     } else if (s.rfind("--skip", 0) == 0) {
       if (!parse_u64(val_of("--skip"), &skip)) { fprintf(stderr, "a5_generator: error: --skip: bad count\n"); return 80; }
       cursor = true;
@@ -571,9 +578,9 @@ int main(int argc, char** argv) {
     });
     std::vector<a5x_hit> first;
     std::vector<uint32_t> first_rule;
-    for (uint64_t k = 0; k < nh && rc == 0; k++) {  // keyed on the full digest (20 / 32 bytes for SHA-1 / SHA-256)
+    for (uint64_t k = 0; k < nh && rc == 0; k++) {  // keyed on the full digest (20 to 64 bytes for the wide algorithms)
       const uint64_t h = ord[k];
-      uint8_t full[32];
+      uint8_t full[64];
       size_t fl = 0;
       if ((rc = a5x_hit_digest(ctx, &hits[h], full, sizeof full, &fl))) break;
       if (cracked.insert(std::string((const char*)full, fl)).second) {

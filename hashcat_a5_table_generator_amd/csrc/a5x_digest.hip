@@ -8,7 +8,8 @@
 //   NTLM  MD4 (RFC 1320) over UTF-16LE of the candidate decoded as Go does for
 //         []rune(string): invalid UTF-8 byte -> U+FFFD, runes > U+FFFF -> surrogate
 //         pairs (unicode/utf16.Encode);
-//   SHA-1 / SHA-256  FIPS 180-4 over the candidate bytes (a5x_sha.h).
+//   SHA-1 / SHA-224 / SHA-256 / SHA-384 / SHA-512  FIPS 180-4 over the candidate bytes
+//         (a5x_sha.h).
 // Each digest is probed against a device-resident target set: a 2^k-bit prefilter
 // indexed by digest word 0, then an open-addressing table of the first 16 digest bytes
 // (wide digests: the remaining words in a parallel array, compared too).
@@ -35,7 +36,7 @@ typedef uint32_t u32;
 
 // stream bytes per wave: 4 KiB for MD5 (lanes stay busy over ~3 rounds of candidates),
 // 2 KiB for NTLM (the MD4 of UTF-16LE costs about twice per candidate byte), 4 KiB for
-// SHA-1 / SHA-256: their time is the hash rounds, and a block's last round of 64 lanes is
+// the SHA algorithms: their time is the hash rounds, and a block's last round of 64 lanes is
 // only part full -- C5's ~23-byte lines give 2 rounds per 2 KiB block, the second 40 %
 // full, against 3 rounds (the third 80 % full) per 4 KiB block; measured on C5 the digest
 // pass takes 83.4 vs 97.3 ms (SHA-1) and 132.4 vs 161.7 ms (SHA-256) at 4 vs 2 KiB
@@ -45,7 +46,10 @@ typedef uint32_t u32;
 #endif
 template <int ALGO> struct DCfg {
   static constexpr u32 BLK = ALGO == A5X_ALGO_MD5 ? 4096u : (ALGO == A5X_ALGO_NTLM ? 2048u : A5X_SHA_DBLK);
-  static constexpr u32 DW = ALGO == A5X_ALGO_SHA1 ? 5u : (ALGO == A5X_ALGO_SHA256 ? 8u : 4u);
+  static constexpr u32 DW = ALGO == A5X_ALGO_SHA1 ? 5u : ALGO == A5X_ALGO_SHA256 ? 8u : ALGO == A5X_ALGO_SHA224 ? 7u
+                          : ALGO == A5X_ALGO_SHA384 ? 12u : ALGO == A5X_ALGO_SHA512 ? 16u : 4u;
+  static constexpr u32 HT = a5x_hit_tail_stride(ALGO);  // words of a hit's tail record
+  static_assert(DW <= 4u || DW - 4u <= HT, "the hit's tail record holds the whole tail");
 };
 constexpr u32 DMARGIN = 256;               // next-block bytes staged for straddling lines
 constexpr u32 D_ERR_HITCAP = 1u << 10;     // more hits than the caller's buffer
@@ -132,7 +136,7 @@ struct DWave {
 };
 
 // op 0: probe targets, record hits; op 1: count line starts per block; op 2: write
-// every candidate's digest at dig_out[4 * DW * (blk_pre[blk] + i)] (16, 20 or 32 bytes)
+// every candidate's digest at dig_out[4 * DW * (blk_pre[blk] + i)] (16 to 64 bytes)
 template <int ALGO>
 __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
   static_assert(DCfg<ALGO>::BLK == 2048u || DCfg<ALGO>::BLK == 4096u, "a5x_digest_lds sizes these two");
@@ -141,6 +145,7 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
   const u32 nwv = blockDim.x / 64;
   constexpr u32 DBLK = DCfg<ALGO>::BLK;
   constexpr u32 DW = DCfg<ALGO>::DW;
+  constexpr u32 HT = DCfg<ALGO>::HT;
   typedef DWave<DBLK> WT;
   constexpr u32 DBUF = WT::BUF;
   constexpr u32 NM = DBLK / 2048u;  // 32-bit newline masks per lane (32 B each)
@@ -257,7 +262,7 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
         if constexpr (DW == 4) {
           uint4* o4 = (uint4*)(a.dig_out + 16 * (a.blk_pre[blk] + i));
           *o4 = make_uint4(d[0], d[1], d[2], d[3]);
-        } else {  // a 20-B stride is only 4-B aligned: dword stores
+        } else {  // a 20-B (28-B) stride is only 4-B aligned: dword stores
           u32* o1 = (u32*)(a.dig_out + 4ull * DW * (a.blk_pre[blk] + i));
 #pragma unroll
           for (u32 k = 0; k < DW; k++) o1[k] = d[k];
@@ -275,7 +280,7 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
           a.hits[h] = r;
           if constexpr (DW > 4) {
 #pragma unroll
-            for (u32 k = 0; k < 4; k++) a.hit_tail[4ull * h + k] = k < DW - 4 ? d[4 + k] : 0u;
+            for (u32 k = 0; k < HT; k++) a.hit_tail[(u64)HT * h + k] = k < DW - 4 ? d[4 + k] : 0u;
           }
         } else {
           err |= D_ERR_HITCAP;
@@ -352,7 +357,9 @@ hipError_t a5x_launch_gather_words(const uint8_t* words, const uint64_t* woff, c
 // the algorithm's stream block (0: not an algorithm)
 static u32 digest_blk(int algo) {
   return algo == A5X_ALGO_MD5 ? DCfg<A5X_ALGO_MD5>::BLK : algo == A5X_ALGO_NTLM ? DCfg<A5X_ALGO_NTLM>::BLK
-       : algo == A5X_ALGO_SHA1 ? DCfg<A5X_ALGO_SHA1>::BLK : algo == A5X_ALGO_SHA256 ? DCfg<A5X_ALGO_SHA256>::BLK : 0u;
+       : algo == A5X_ALGO_SHA1 ? DCfg<A5X_ALGO_SHA1>::BLK : algo == A5X_ALGO_SHA256 ? DCfg<A5X_ALGO_SHA256>::BLK
+       : algo == A5X_ALGO_SHA224 ? DCfg<A5X_ALGO_SHA224>::BLK : algo == A5X_ALGO_SHA384 ? DCfg<A5X_ALGO_SHA384>::BLK
+       : algo == A5X_ALGO_SHA512 ? DCfg<A5X_ALGO_SHA512>::BLK : 0u;
 }
 size_t a5x_digest_lds(int algo) {
   const u32 blk = digest_blk(algo);
@@ -376,6 +383,12 @@ hipError_t a5x_launch_digest_stream(const A5xDigLaunch& L, int op, uint32_t grid
     hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA1>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
   else if (L.algo == A5X_ALGO_SHA256)
     hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA256>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+  else if (L.algo == A5X_ALGO_SHA224)
+    hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA224>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+  else if (L.algo == A5X_ALGO_SHA384)
+    hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA384>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+  else if (L.algo == A5X_ALGO_SHA512)
+    hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA512>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
   else
     return hipErrorInvalidValue;  // a missing kernel is an error, never another algorithm's digest
   return hipGetLastError();

@@ -122,16 +122,16 @@ struct a5x_ctx {
   DevBuf<uint8_t> dg_scratch;
   DevBuf<uint64_t> dg_blk_cnt, dg_blk_pre, dg_cand_off, dg_byte_off;
   DevBuf<A5xHitRaw> dg_hits;
-  // wide algorithms (SHA-1 / SHA-256): t_tw tail words per digest past the first four --
-  // per table slot (t_tails), of the zero-prefix targets (t_ztails), per device hit
-  // (dg_hit_tail, 4 words each); the sorted unique digests on the host (a5x_hit_digest),
+  // wide algorithms (SHA-1 and the SHA-2 family): t_tw tail words per digest past the first
+  // four -- per table slot (t_tails), of the zero-prefix targets (t_ztails), per device hit
+  // (dg_hit_tail, a5x_hit_tail_stride words each); the sorted unique digests on the host (a5x_hit_digest),
   // whether two of them share their first 16 bytes, and for such prefixes the tails the
   // latest expand_digest call's hits matched, keyed by (word, cand)
   uint32_t t_tw = 0, t_nz = 0;
   DevBuf<uint32_t> t_tails, t_ztails, dg_hit_tail;
   std::vector<uint8_t> t_full;
   bool t_shared_prefix = false;
-  std::map<std::pair<uint64_t, uint64_t>, std::array<uint32_t, 4>> t_hit_tails;
+  std::map<std::pair<uint64_t, uint64_t>, std::array<uint32_t, 12>> t_hit_tails;
   hipEvent_t dev_ev[2] = {nullptr, nullptr};
   // rules (a5x_rules.hip): the accepted rules as a table of A5X_RULE_STRIDE u32 each (host
   // copy + device copy), and of the latest digest call: each copied hit's rule, the lines
@@ -1270,7 +1270,15 @@ A5xDigLaunch dig_launch(a5x_ctx* c) {
 
 // digest bytes per algorithm (a5x_digest_size), 0: not an algorithm
 inline uint32_t algo_size(int algo) {
-  return algo == A5X_ALGO_MD5 || algo == A5X_ALGO_NTLM ? 16u : algo == A5X_ALGO_SHA1 ? 20u : algo == A5X_ALGO_SHA256 ? 32u : 0u;
+  switch (algo) {
+    case A5X_ALGO_MD5: case A5X_ALGO_NTLM: return 16u;
+    case A5X_ALGO_SHA1: return 20u;
+    case A5X_ALGO_SHA256: return 32u;
+    case A5X_ALGO_SHA224: return 28u;
+    case A5X_ALGO_SHA384: return 48u;
+    case A5X_ALGO_SHA512: return 64u;
+    default: return 0u;  // (4 is unassigned)
+  }
 }
 
 // the context's sorted unique wide digests, in place
@@ -1317,7 +1325,7 @@ void build_target_set(uint32_t W, const uint8_t* dig, uint64_t n, TargetSet& T) 
   uint32_t has_zero = 0;
   const uint64_t tmask = tsz - 1;
   for (uint64_t i = 0; i < n; i++) {
-    uint32_t d[8];
+    uint32_t d[16];
     memcpy(d, dig + (uint64_t)W * i, W);
     if ((d[0] | d[1] | d[2] | d[3]) == 0) {
       has_zero = 1;
@@ -1346,7 +1354,13 @@ void build_target_set(uint32_t W, const uint8_t* dig, uint64_t n, TargetSet& T) 
   bool shared = false;
   if (TW) {
     full.assign(dig, dig + (uint64_t)W * n);
-    if (W == 20) sort_unique_digests<20>(full); else sort_unique_digests<32>(full);
+    switch (W) {
+      case 20: sort_unique_digests<20>(full); break;
+      case 28: sort_unique_digests<28>(full); break;
+      case 32: sort_unique_digests<32>(full); break;
+      case 48: sort_unique_digests<48>(full); break;
+      default: sort_unique_digests<64>(full); break;
+    }
     for (size_t i = 1; i < full.size() / W && !shared; i++)
       shared = memcmp(&full[(i - 1) * W], &full[i * W], 16) == 0;
   }
@@ -1442,7 +1456,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
                   uint64_t rb, uint64_t re, uint64_t scratch_bytes, a5x_hit* hits, uint64_t hit_cap,
                   uint64_t* n_hits, a5x_stats* stats, hipStream_t st, bool allow_fused, uint64_t trim = 0) {
   int rc;
-  // SHA-1 / SHA-256: the two-pass range loop in every mode (no fused kernel hashes them)
+  // SHA-1 and the SHA-2 family: the two-pass range loop in every mode (no fused kernel hashes them)
   const bool wide = c->t_tw != 0;
   if (wide) {
     allow_fused = false;
@@ -1650,7 +1664,8 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   if ((rc = grow(c, c->dg_scratch, cap + 64))) return rc;
   uint64_t dev_hits = std::max<uint64_t>(1024, std::min<uint64_t>(hit_cap, 1u << 20));
   if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
-  if (wide && (rc = grow(c, c->dg_hit_tail, 4 * dev_hits))) return rc;
+  const uint32_t HT = a5x_hit_tail_stride(c->t_algo);  // tail words the kernels record per hit
+  if (wide && (rc = grow(c, c->dg_hit_tail, (uint64_t)HT * dev_hits))) return rc;
   if (ruled && ((rc = grow(c, c->dg_hit_rule, dev_hits)) || (rc = grow(c, c->r_counter, 2)))) return rc;
   std::vector<uint32_t> htail;  // wide: the range's hit tails
   a5x_stats total;
@@ -1715,7 +1730,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       if (nh <= dev_hits || copied >= hit_cap) break;
       dev_hits = nh;  // grow and run this range's digest again (its candidates are still in scratch)
       if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
-      if (wide && (rc = grow(c, c->dg_hit_tail, 4 * dev_hits))) return rc;
+      if (wide && (rc = grow(c, c->dg_hit_tail, (uint64_t)HT * dev_hits))) return rc;
       if (ruled && (rc = grow(c, c->dg_hit_rule, dev_hits))) return rc;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 2, 0, 4, J.st));
     }
@@ -1734,8 +1749,8 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       if (take)
         HIPCHK(c, hipMemcpyAsync(hits + copied, c->dg_hits.p, take * sizeof(a5x_hit), hipMemcpyDeviceToHost, J.st));
       if (take && c->t_shared_prefix) {
-        htail.resize(4 * take);
-        HIPCHK(c, hipMemcpyAsync(htail.data(), c->dg_hit_tail.p, take * 16, hipMemcpyDeviceToHost, J.st));
+        htail.resize(HT * take);
+        HIPCHK(c, hipMemcpyAsync(htail.data(), c->dg_hit_tail.p, take * 4 * HT, hipMemcpyDeviceToHost, J.st));
       }
       if (take && ruled) {
         c->r_hit_rule.resize(copied + take);
@@ -1743,9 +1758,11 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       }
       HIPCHK(c, hipStreamSynchronize(J.st));
       if (take && c->t_shared_prefix)  // (which of the targets sharing a prefix each hit matched: a5x_hit_digest)
-        for (uint64_t k = 0; k < take; k++)
-          c->t_hit_tails[std::make_pair(hits[copied + k].word, hits[copied + k].cand)] = {
-              htail[4 * k], htail[4 * k + 1], htail[4 * k + 2], htail[4 * k + 3]};
+        for (uint64_t k = 0; k < take; k++) {
+          std::array<uint32_t, 12>& t = c->t_hit_tails[std::make_pair(hits[copied + k].word, hits[copied + k].cand)];
+          t.fill(0u);
+          memcpy(t.data(), &htail[HT * k], 4 * HT);
+        }
       copied += take;
       found += nh;
     }
@@ -2598,7 +2615,7 @@ int a5x_hit_digest(a5x_ctx* c, const a5x_hit* hit, uint8_t* out, size_t cap, siz
   *out_len = W;
   if (!out) return A5X_OK;
   if (cap < W) return fail(c, A5X_E_CAPACITY, "digest of %u bytes, buffer has %zu", W, cap);
-  uint8_t d[32];
+  uint8_t d[64];
   const int rc = hit_full_digest(c, hit, d);
   if (rc) return rc;
   memcpy(out, d, W);
@@ -2606,15 +2623,20 @@ int a5x_hit_digest(a5x_ctx* c, const a5x_hit* hit, uint8_t* out, size_t cap, siz
 }
 
 int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, size_t cap) {
-  if ((algo != A5X_ALGO_SHA1 && algo != A5X_ALGO_SHA256) || (!msg && len) || !out || len > 0xffffff00u) return A5X_E_ARG;
+  if (algo < A5X_ALGO_SHA1 || !algo_size(algo) || (!msg && len) || !out || len > 0xffffff00u) return A5X_E_ARG;
   const uint32_t W = algo_size(algo);
   if (cap < W) return A5X_E_CAPACITY;
   ShaBytes src;
   src.p = msg;
   src.n = (uint32_t)len;
-  uint32_t d[8];
-  if (algo == A5X_ALGO_SHA1) sha_digest<A5X_ALGO_SHA1>(src, (uint32_t)len, d);
-  else sha_digest<A5X_ALGO_SHA256>(src, (uint32_t)len, d);
+  uint32_t d[16];
+  switch (algo) {
+    case A5X_ALGO_SHA1: sha_digest<A5X_ALGO_SHA1>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_SHA256: sha_digest<A5X_ALGO_SHA256>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_SHA224: sha_digest<A5X_ALGO_SHA224>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_SHA384: sha_digest<A5X_ALGO_SHA384>(src, (uint32_t)len, d); break;
+    default: sha_digest<A5X_ALGO_SHA512>(src, (uint32_t)len, d); break;
+  }
   memcpy(out, d, W);
   return A5X_OK;
 }

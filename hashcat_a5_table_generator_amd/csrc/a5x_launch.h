@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "a5x.h"
+
 struct A5xKsLaunch {
   const uint8_t* table;
   uint32_t table_bytes;
@@ -257,16 +259,19 @@ struct A5xDigLaunch {
   const uint64_t* blk_pre;  // op 2 / resolve input (exclusive scan of blk_cnt)
   uint8_t* dig_out;         // op 2 output: a5x_digest_size(algo) bytes per candidate
   uint32_t* err;
-  // wide algorithms (SHA-1: 1 tail word, SHA-256: 4): the digest words past the first
-  // four of every table slot, the tails of the targets whose first 16 bytes are zero
-  // (has_zero_target), and per hit the tail that matched (4 words each, hit order)
+  // wide algorithms (tail words: SHA-1 1, SHA-224 3, SHA-256 4, SHA-384 8, SHA-512 12): the
+  // digest words past the first four of every table slot, the tails of the targets whose
+  // first 16 bytes are zero (has_zero_target), and per hit the tail that matched, in hit
+  // order at a stride of a5x_hit_tail_stride(algo) words: 4 for SHA-1 / SHA-256, 12 for
+  // SHA-224 / SHA-384 / SHA-512 (words past the algorithm's tail are zero)
   const uint32_t* tails;
   const uint32_t* ztails;
   uint32_t nztails;
   uint32_t* hit_tail;
 };
+constexpr uint32_t a5x_hit_tail_stride(int algo) { return algo >= A5X_ALGO_SHA224 ? 12u : 4u; }
 size_t a5x_digest_lds(int algo);
-uint64_t a5x_digest_blocks(uint64_t nbytes, int algo);  // 2 KiB (NTLM) / 4 KiB (MD5, SHA-1, SHA-256) blocks
+uint64_t a5x_digest_blocks(uint64_t nbytes, int algo);  // 2 KiB (NTLM) / 4 KiB (MD5, SHA-*) blocks
 hipError_t a5x_launch_digest_stream(const A5xDigLaunch& L, int op, uint32_t grid, hipStream_t st);
 // hybrid fused digest: list the candidate-bearing non-FAST words (n: device counter),
 // then gather them into a sub-batch (lens != null: their lengths; else the bytes at sub_off)

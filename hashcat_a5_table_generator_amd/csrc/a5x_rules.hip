@@ -37,7 +37,10 @@ static_assert(RMARGIN >= A5X_RULE_LMAX + 1u, "a rule-sized line that starts in a
 static_assert(A5X_RULE_NDW * 4u >= A5X_RULE_LMAX + 8u, "the hash sources read up to 8 bytes past the message");
 
 template <int ALGO> struct RCfg {
-  static constexpr u32 DW = ALGO == A5X_ALGO_SHA1 ? 5u : (ALGO == A5X_ALGO_SHA256 ? 8u : 4u);
+  static constexpr u32 DW = ALGO == A5X_ALGO_SHA1 ? 5u : ALGO == A5X_ALGO_SHA256 ? 8u : ALGO == A5X_ALGO_SHA224 ? 7u
+                          : ALGO == A5X_ALGO_SHA384 ? 12u : ALGO == A5X_ALGO_SHA512 ? 16u : 4u;
+  static constexpr u32 HT = a5x_hit_tail_stride(ALGO);  // words of a hit's tail record
+  static_assert(DW <= 4u || DW - 4u <= HT, "the hit's tail record holds the whole tail");
 };
 
 struct RWave {
@@ -103,6 +106,7 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
   const u32 wv = threadIdx.x / 64, lane = __lane_id();
   const u32 nwv = blockDim.x / 64;
   constexpr u32 DW = RCfg<ALGO>::DW;
+  constexpr u32 HT = RCfg<ALGO>::HT;
   constexpr u32 DBUF = RWave::BUF;
   constexpr u32 NM = RBLK / 2048u;  // 32-bit newline masks per lane (32 B each)
   static_assert(NM == 2, "a lane's starts are kept in one 64-bit mask");
@@ -248,7 +252,7 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
             q.hit_rule[h] = r;
             if constexpr (DW > 4) {
 #pragma unroll
-              for (u32 k = 0; k < 4; k++) a.hit_tail[4ull * h + k] = k < DW - 4 ? d[4 + k] : 0u;
+              for (u32 k = 0; k < HT; k++) a.hit_tail[(u64)HT * h + k] = k < DW - 4 ? d[4 + k] : 0u;
             }
           } else {
             err |= R_ERR_HITCAP;
@@ -263,48 +267,64 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
 
 }  // namespace
 
+// grid and launch of one instantiation.  The grid is exactly the waves the device holds at
+// once (cus x resident workgroups): every wave takes the same share of the blocks in its
+// grid-stride loop.  A larger grid runs a second, part-empty residency round -- 16 waves per
+// CU launched against 12 resident cost 0.72-0.85 of the no-rule stream's hash rate where this
+// gives DESIGN "Rules"'s figures.
+template <int ALGO>
+static hipError_t rules_launch(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st) {
+  const u64 want = (a5x_rules_blocks(L.d.nbytes) + RWAVES - 1) / RWAVES;
+  const size_t lds = a5x_rules_lds();
+  // workgroups of k_rules_stream<ALGO> one CU holds at once (LDS: 3; fewer if the registers say so)
+  static int per_cu = 0;
+  if (!per_cu) {
+    int v = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_rules_stream<ALGO>, 64 * RWAVES, lds) != hipSuccess || v < 1)
+      v = 2;  // (2 waves per SIMD)
+    per_cu = v;
+  }
+  const u64 grid = (u64)(cus ? cus : 1u) * (u32)per_cu;
+  const u32 g = (u32)(want < grid ? want : grid);
+  hipLaunchKernelGGL(k_rules_stream<ALGO>, dim3(g), dim3(64 * RWAVES), lds, st, L, op);
+  return hipGetLastError();
+}
+
+// The instantiations live in two translation units: MD5 / NTLM / SHA-1 / SHA-256 here, SHA-224
+// / SHA-384 / SHA-512 in a5x_rules_wide.hip, which includes this file with A5X_RULES_WIDE
+// defined.  The compiler's inlining of the rule interpreter depends on how many kernels of a
+// module call it: with seven in one module the first four's code changed, in a module of their
+// own it is instruction-identical to what it was (DESIGN "SHA-224, SHA-384 and SHA-512").
+#ifndef A5X_RULES_WIDE
 size_t a5x_rules_lds() { return RWAVES * ((sizeof(RWave) + 15u) & ~15u); }
 
 uint64_t a5x_rules_blocks(uint64_t nbytes) { return (nbytes + RBLK - 1) / RBLK; }
 
-// workgroups of k_rules_stream<ALGO> one CU holds at once (LDS: 3; fewer if the registers say so)
-template <int ALGO>
-static u32 rules_resident(size_t lds) {
-  static int n = 0;
-  if (!n) {
-    int v = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_rules_stream<ALGO>, 64 * RWAVES, lds) != hipSuccess || v < 1)
-      v = 2;  // (2 waves per SIMD)
-    n = v;
-  }
-  return (u32)n;
-}
+hipError_t a5x_launch_rules_stream_wide(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st);
 
-// The grid is exactly the waves the device holds at once (cus x resident workgroups): every
-// wave takes the same share of the blocks in its grid-stride loop.  A larger grid runs a
-// second, part-empty residency round -- 16 waves per CU launched against 12 resident cost 0.72-0.85
-// of the no-rule stream's hash rate where this gives DESIGN "Rules"'s figures.
 hipError_t a5x_launch_rules_stream(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st) {
   if (L.d.nbytes == 0) return hipSuccess;
   if (((uintptr_t)L.d.out & 15u) != 0) return hipErrorInvalidValue;
   if (op != 1 && (!L.rules || !L.nrules || !L.rejected)) return hipErrorInvalidValue;
   if (op == 0 && (!L.hit_rule || (L.d.algo >= A5X_ALGO_SHA1 && (!L.d.hit_tail || !L.d.tails)))) return hipErrorInvalidValue;
-  const u64 want = (a5x_rules_blocks(L.d.nbytes) + RWAVES - 1) / RWAVES;
-  const size_t lds = a5x_rules_lds();
-  const u32 per_cu = L.d.algo == A5X_ALGO_MD5 ? rules_resident<A5X_ALGO_MD5>(lds)
-                   : L.d.algo == A5X_ALGO_NTLM ? rules_resident<A5X_ALGO_NTLM>(lds)
-                   : L.d.algo == A5X_ALGO_SHA1 ? rules_resident<A5X_ALGO_SHA1>(lds)
-                   : L.d.algo == A5X_ALGO_SHA256 ? rules_resident<A5X_ALGO_SHA256>(lds) : 0u;
-  if (!per_cu) return hipErrorInvalidValue;  // a missing kernel is an error, never another algorithm's digest
-  const u64 grid = (u64)(cus ? cus : 1u) * per_cu;
-  const u32 g = (u32)(want < grid ? want : grid);
-  if (L.d.algo == A5X_ALGO_MD5)
-    hipLaunchKernelGGL(k_rules_stream<A5X_ALGO_MD5>, dim3(g), dim3(64 * RWAVES), lds, st, L, op);
-  else if (L.d.algo == A5X_ALGO_NTLM)
-    hipLaunchKernelGGL(k_rules_stream<A5X_ALGO_NTLM>, dim3(g), dim3(64 * RWAVES), lds, st, L, op);
-  else if (L.d.algo == A5X_ALGO_SHA1)
-    hipLaunchKernelGGL(k_rules_stream<A5X_ALGO_SHA1>, dim3(g), dim3(64 * RWAVES), lds, st, L, op);
-  else
-    hipLaunchKernelGGL(k_rules_stream<A5X_ALGO_SHA256>, dim3(g), dim3(64 * RWAVES), lds, st, L, op);
-  return hipGetLastError();
+  switch (L.d.algo) {
+    case A5X_ALGO_MD5: return rules_launch<A5X_ALGO_MD5>(L, op, cus, st);
+    case A5X_ALGO_NTLM: return rules_launch<A5X_ALGO_NTLM>(L, op, cus, st);
+    case A5X_ALGO_SHA1: return rules_launch<A5X_ALGO_SHA1>(L, op, cus, st);
+    case A5X_ALGO_SHA256: return rules_launch<A5X_ALGO_SHA256>(L, op, cus, st);
+    case A5X_ALGO_SHA224: case A5X_ALGO_SHA384: case A5X_ALGO_SHA512:
+      return a5x_launch_rules_stream_wide(L, op, cus, st);
+    default: return hipErrorInvalidValue;  // a missing kernel is an error, never another algorithm's digest
+  }
 }
+#else
+// (arguments checked by a5x_launch_rules_stream)
+hipError_t a5x_launch_rules_stream_wide(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st) {
+  switch (L.d.algo) {
+    case A5X_ALGO_SHA224: return rules_launch<A5X_ALGO_SHA224>(L, op, cus, st);
+    case A5X_ALGO_SHA384: return rules_launch<A5X_ALGO_SHA384>(L, op, cus, st);
+    case A5X_ALGO_SHA512: return rules_launch<A5X_ALGO_SHA512>(L, op, cus, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+#endif

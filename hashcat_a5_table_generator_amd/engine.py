@@ -38,12 +38,17 @@ ALGO_MD5 = 0   # RFC 1321 (Go crypto/md5)
 ALGO_NTLM = 1  # MD4 over UTF-16LE ([]rune + utf16.Encode)
 ALGO_SHA1 = 2  # FIPS 180-4 over the candidate bytes (hashcat -m 100)
 ALGO_SHA256 = 3  # FIPS 180-4 over the candidate bytes (hashcat -m 1400)
+# (4 is unassigned)
+ALGO_SHA224 = 5  # FIPS 180-4 over the candidate bytes (hashcat -m 1300)
+ALGO_SHA384 = 6  # FIPS 180-4 over the candidate bytes (hashcat -m 10800)
+ALGO_SHA512 = 7  # FIPS 180-4 over the candidate bytes (hashcat -m 1700)
 
 SubMap = Dict[bytes, List[bytes]]
 
 
 def digest_size(algo: int) -> int:
-    """Digest bytes of an algorithm (``a5x_digest_size``): 16, 16, 20, 32."""
+    """Digest bytes of an algorithm (``a5x_digest_size``): 16, 16, 20, 32 for MD5, NTLM, SHA-1, SHA-256 and
+    28, 48, 64 for SHA-224, SHA-384, SHA-512."""
     n = _lib.load().a5x_digest_size(algo)
     if n < 0:
         raise A5xError(n, f"bad digest algorithm {algo}")
@@ -237,13 +242,13 @@ class Context:
 
     def hit_digest(self, hit) -> bytes:
         """The full digest of a hit ``(word, cand, digest)`` against the current target set
-        (``a5x_hit_digest``): for SHA-1 / SHA-256 the target that the hit's 16 digest bytes begin."""
+        (``a5x_hit_digest``): for SHA-1 and the SHA-2 family the target that the hit's 16 digest bytes begin."""
         h = _lib.Hit()
         h.word, h.cand = int(hit[0]), int(hit[1])
         ctypes.memmove(h.digest, bytes(hit[2])[:16], 16)
-        out = (ctypes.c_uint8 * 32)()
+        out = (ctypes.c_uint8 * 64)()
         n = ctypes.c_size_t()
-        self._chk(self._L.a5x_hit_digest(self.h, ctypes.byref(h), out, 32, ctypes.byref(n)))
+        self._chk(self._L.a5x_hit_digest(self.h, ctypes.byref(h), out, 64, ctypes.byref(n)))
         return bytes(out[: n.value])
 
     def _hits(self, arr, n) -> List[Tuple[int, int, bytes]]:

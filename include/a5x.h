@@ -61,20 +61,24 @@ enum {
   A5X_MODE_SUBALL_REVERSE = 3
 };
 
-/* digest algorithms of the fused digest + lookup stage */
+/* digest algorithms of the fused digest + lookup stage.  Value 4 is
+ * unassigned and invalid (A5X_E_ARG everywhere); additions never renumber. */
 enum {
   A5X_ALGO_MD5 = 0,   /* RFC 1321 over the candidate bytes (== Go crypto/md5); hashcat -m 0 */
   A5X_ALGO_NTLM = 1,  /* MD4 (RFC 1320) over UTF-16LE of the candidate ([]rune + utf16.Encode); -m 1000 */
   A5X_ALGO_SHA1 = 2,  /* SHA-1 (FIPS 180-4) over the candidate bytes; hashcat -m 100 */
-  A5X_ALGO_SHA256 = 3 /* SHA-256 (FIPS 180-4) over the candidate bytes; hashcat -m 1400 */
+  A5X_ALGO_SHA256 = 3, /* SHA-256 (FIPS 180-4) over the candidate bytes; hashcat -m 1400 */
+  A5X_ALGO_SHA224 = 5, /* SHA-224 (FIPS 180-4) over the candidate bytes; hashcat -m 1300 */
+  A5X_ALGO_SHA384 = 6, /* SHA-384 (FIPS 180-4) over the candidate bytes; hashcat -m 10800 */
+  A5X_ALGO_SHA512 = 7  /* SHA-512 (FIPS 180-4) over the candidate bytes; hashcat -m 1700 */
 };
-/* Digest bytes of an algorithm: 16, 16, 20, 32; A5X_E_ARG for anything else.  Pure host
- * function (no HIP call). */
+/* Digest bytes of an algorithm: 16, 16, 20, 32 for 0..3 and 28, 48, 64 for 5..7; A5X_E_ARG
+ * for anything else (4 included).  Pure host function (no HIP call). */
 A5X_API int a5x_digest_size(int algo);
 
 /* One target hit: word index in the batch, candidate index inside that word (in the
  * library's per-word candidate order, the one a5x_expand emits), digest bytes.  For an
- * algorithm wider than 16 bytes (SHA-1, SHA-256) digest holds the first 16 bytes of the
+ * algorithm wider than 16 bytes (SHA-1, SHA-224 / 256 / 384 / 512) digest holds the first 16 bytes of the
  * candidate's digest; the whole digest matched a target, and a5x_hit_digest returns it. */
 typedef struct a5x_hit {
   uint64_t word;
@@ -186,12 +190,12 @@ A5X_API int a5x_digest_device(a5x_ctx* ctx, const uint8_t* d_out, const uint64_t
 /* Replace the device-resident target set: n digests of algorithm algo, each
  * a5x_digest_size(algo) bytes in the digest's standard byte order (duplicates allowed).
  * Built on the host (prefilter bitmap + open-addressing table keyed on the first 16
- * bytes, the remaining bytes in a parallel array) and uploaded once.  For the wide
- * algorithms the context keeps a host copy of the digests for a5x_hit_digest. */
+ * bytes, the remaining 4 to 48 bytes in a parallel array) and uploaded once.  For the wide
+ * algorithms (SHA-1 and the SHA-2 family) the context keeps a host copy of the digests for a5x_hit_digest. */
 A5X_API int a5x_set_targets(a5x_ctx* ctx, int algo, const uint8_t* digests, uint64_t n);
 /* The full digest of a hit against the context's current target set, *out_len =
- * a5x_digest_size of the set's algorithm: the hit's own 16 bytes for MD5 / NTLM, else
- * the target whose first 16 bytes equal hit->digest (A5X_E_ARG when there is none;
+ * a5x_digest_size of the set's algorithm (at most 64): the hit's own 16 bytes for MD5 /
+ * NTLM, else the target whose first 16 bytes equal hit->digest (A5X_E_ARG when there is none;
  * should several targets share those 16 bytes, the one that the hit (word, cand) of the
  * context's latest a5x_expand_digest* call matched).  out == NULL: size only;
  * A5X_E_CAPACITY when cap is too small.  Host only. */
@@ -221,7 +225,7 @@ A5X_API int a5x_expand_digest(a5x_ctx* ctx, const uint8_t* words, const uint64_t
 /* Digest of every line of a device "cand\n" stream (d_lines 16-B aligned, nbytes
  * ending in '\n') into d_digests (a5x_digest_size(algo) bytes per line, in line order,
  * in the digest's standard byte order; 16-B aligned for MD5 / NTLM, 4-B aligned for the
- * wide algorithms); digests_cap counts lines; *n_lines = lines.
+ * wide algorithms: 20 / 28 / 32 / 48 / 64 bytes per line); digests_cap counts lines; *n_lines = lines.
  * Verification hook for the digest kernels (tests compare with hashlib / RFC MD4). */
 A5X_API int a5x_digest_lines_device(a5x_ctx* ctx, int algo, const uint8_t* d_lines, uint64_t nbytes,
                                     uint8_t* d_digests, uint64_t digests_cap, uint64_t* n_lines, void* stream);
@@ -233,8 +237,9 @@ A5X_API int a5x_digest_lines_device(a5x_ctx* ctx, int algo, const uint8_t* d_lin
  * out == NULL: size only; A5X_E_CAPACITY when cap is too small.  Pure host function. */
 A5X_API int a5x_format_plain(const uint8_t* plain, size_t len, uint8_t* out, size_t cap, size_t* out_len);
 /* One "hexdigest:plain\n" line per hit, in hit order, through sink (hashcat -m 0 /
- * -m 1000 / -m 100 / -m 1400 potfile form, README.MD:74-106; the full-width digest, 40
- * or 64 hex digits for SHA-1 / SHA-256, obtained as in a5x_hit_digest): the plains are
+ * -m 1000 / -m 100 / -m 1400 / -m 1300 / -m 10800 / -m 1700 potfile form, README.MD:74-106;
+ * the full-width digest, 40 / 64 / 56 / 96 / 128 hex digits for SHA-1 / SHA-256 / SHA-224 /
+ * SHA-384 / SHA-512, obtained as in a5x_hit_digest): the plains are
  * regenerated on the device from the hit's (word, cand) with the same batch (host
  * buffers), mode and limits the hits were found with. */
 A5X_API int a5x_format_hits(a5x_ctx* ctx, const uint8_t* words, const uint64_t* word_off, uint64_t n_words,
@@ -323,7 +328,7 @@ A5X_API int a5x_debug_plan_word(a5x_ctx* ctx, const uint8_t* word, size_t len, i
 A5X_API int a5x_debug_plan_sizes(a5x_ctx* ctx, const uint8_t* word, size_t len, uint32_t* out);
 
 /* Test hook (CPU test suite): the digest of msg[0, len) computed on the host by the
- * __host__ __device__ core the digest kernels run (a5x_sha.h; SHA-1 and SHA-256 only),
+ * __host__ __device__ core the digest kernels run (a5x_sha.h; SHA-1 and the SHA-2 family),
  * a5x_digest_size(algo) bytes into out.  Never called by a compute path. */
 A5X_API int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, size_t cap);
 

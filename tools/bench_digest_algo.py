@@ -1,17 +1,18 @@
-"""Two-pass digest + lookup rate per algorithm on one GPU (SHA-1 / SHA-256 beside MD5).
+"""Two-pass digest + lookup rate per algorithm on one GPU (the SHA family beside MD5).
 
 Workload C5 as bench.py --workload c5 builds it (greek-hebrew x the synthetic Greek words
 of synth.py), default mode, 1M random targets of the algorithm's width,
 a5x_expand_digest_device.  Every algorithm runs the two-pass route (expand into the
-device scratch, k_digest_stream, k_hits_resolve): SHA-1 / SHA-256 always do, MD5 / NTLM
+device scratch, k_digest_stream, k_hits_resolve): the SHA algorithms always do, MD5 / NTLM
 are forced onto it with A5X_NO_FUSED_DIGEST=1 -- the yardstick, same expansion kernels.
 One context per algorithm, the timed steps alternate between them; per step the library's
 own split (HIP events): keyspace, expansion, digest = total - keyspace - expansion.
 
     python tools/bench_digest_algo.py [--words N] [--steps K] [--warmup W] [--isa-mix FILE] [--out FILE]
 
---isa-mix: the JSON tools/isa_mix.py wrote (CPU); its per-64-byte-block VALU counts are
-copied into the record beside the rates.
+--isa-mix: the JSON tools/isa_mix.py wrote (CPU); its per-block VALU counts (64-byte blocks;
+128-byte for sha384 / sha512) are copied into the record beside the rates.  With sha256 among
+--algos every other algorithm's digest-pass time is also given as a ratio of SHA-256's.
 """
 import argparse
 import json
@@ -25,8 +26,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-NAMES = {"md5": 0, "ntlm": 1, "sha1": 2, "sha256": 3}
-BLOCK_FN = {"md5": "md5_block", "ntlm": "md4_block", "sha1": "sha1_block", "sha256": "sha256_block"}
+NAMES = {"md5": 0, "ntlm": 1, "sha1": 2, "sha256": 3, "sha224": 5, "sha384": 6, "sha512": 7}
+BLOCK_FN = {"md5": "md5_block", "ntlm": "md4_block", "sha1": "sha1_block", "sha256": "sha256_block",
+            "sha224": "sha256_block", "sha384": "sha512_block", "sha512": "sha512_block"}
 
 
 def main():
@@ -93,9 +95,12 @@ def main():
              "digest_candidates_per_s": s[0]["candidates"] / (statistics.median(dig) * 1e-3)}
         m = isa.get(BLOCK_FN[name])
         if m:
-            r["isa_per_64_byte_block"] = {"function": BLOCK_FN[name], "valu_instructions": m["valu_instructions"],
-                                          "half_rate_instructions": round(m["half_rate_share"] * m["valu_instructions"]),
-                                          "mean_issue_cycles": m["mean_issue_cycles"]}
+            r["isa_per_block"] = {"block_bytes": 128 if BLOCK_FN[name] == "sha512_block" else 64, "function": BLOCK_FN[name], "valu_instructions": m["valu_instructions"],
+                                  "half_rate_instructions": round(m["half_rate_share"] * m["valu_instructions"]),
+                                  "mean_issue_cycles": m["mean_issue_cycles"]}
+        if "sha256" in runs and name != "sha256":
+            y = statistics.median(x["ms_total"] - x["ms_keyspace"] - x["ms_expand"] for x in runs["sha256"]["steps"])
+            r["digest_ms_over_sha256"] = statistics.median(dig) / y
         res["algos"][name] = r
         print(f"{name:7s} {r['candidates_per_s']:.3e} cand/s  wall {r['wall_ms']['median']:.2f} ms  keyspace "
               f"{r['ms_keyspace']:.2f}  expand {r['ms_expand']['median']:.2f} ({r['ms_expand']['min']:.2f}-"

@@ -26,7 +26,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-NAMES = {"md5": 0, "ntlm": 1, "sha1": 2, "sha256": 3}
+NAMES = {"md5": 0, "ntlm": 1, "sha1": 2, "sha256": 3, "sha224": 5, "sha384": 6, "sha512": 7}
 MIX = ["l", "u", "c", "$1", "$2", "$3", "$!", "$s", "^1", "^a", "sa@", "se3", "so0", "si1", "r", "d", "T0", "T1", "T2",
        "]", "l$1", "u$1", "c$1", "c$!", "l]", "u]", "c]", "r$1", "d]", "T0$1", "c$1$2", "c$2$0", "l$1$2$3", "sa@c",
        "se3u", "so0l", "^1$1", "^!$!", "T0T1", "T1T2", "]]", "]$s", "]$1", "c]$1", "rc", "rl", "ru", "r]", "dl",

@@ -6,8 +6,8 @@ v_bitop3_b32 / v_add_u32_e64 / v_cmp / v_cndmask issue in ~2 cycles (the chip's 
 32 lanes per cycle), v_add3_u32 / v_alignbit_b32 / v_bfi_b32 / v_perm_b32 / v_alignbyte_b32 /
 v_lshl_or_b32 / v_lshl_add_u32 / v_lshlrev_b32_e64 / v_mul_hi_u32 in ~4 (half rate).
 This tool compiles md5_block / md4_block (csrc/a5x_md.h) and sha1_block / sha256_block
-(csrc/a5x_sha.h; per 64-byte block, with the 16 byte swaps of its message words) on runtime
-data and the whole
+(csrc/a5x_sha.h; per 64-byte block, with the 16 byte swaps of its message words) and
+sha512_block (per 128-byte block, with its 32 byte swaps) on runtime data and the whole
 k_expand_fast_md5 / _ntlm kernels, counts every VALU opcode and prices it, giving the mean
 SIMD cycles per VALU instruction of each stream -> the mix-weighted VALU peak
 (256 CUs x 4 SIMDs x 64 lanes x clock / mean cycles) that bench.py reports beside the nominal
@@ -30,6 +30,7 @@ MEASURED = {  # profiles/r06_mb_valu.txt, 4 waves per SIMD, rounded to the issue
     "v_add_u32_e32": 2, "v_xor_b32_e32": 2, "v_bitop3_b32": 2, "v_add_u32_e64": 2, "v_cndmask_b32_e32": 2,
     "v_cmp_gt_u32_e32": 2, "v_add3_u32": 4, "v_xad_u32": 4, "v_bfi_b32": 4, "v_alignbit_b32": 4, "v_perm_b32": 4,
     "v_alignbyte_b32": 4, "v_lshl_or_b32": 4, "v_lshl_add_u32": 4, "v_mul_hi_u32": 4, "v_lshlrev_b32_e64": 4,
+    "v_lshl_add_u64": 4,  # profiles/r09_mb_valu.txt (a v_add_co_u32 + v_addc_co_u32 pair: 4 each, 8 per 64-bit add)
 }
 HALF = re.compile(r"^v_(add3|xad|bfi|align|perm|lshl_|lshr|ashr|mul|mad|bfe|lshl|lshlrev|lshrrev|ashrrev|alignbit|"
                   r"alignbyte|readlane|writelane|sad|cvt|bcnt|ffbh|ffbl|mbcnt)")
@@ -65,6 +66,17 @@ __global__ void p_sha1(const uint32_t* in, uint32_t* out) {
   for (int i = 0; i < 16; i++) M[i] = sha_bswap(in[threadIdx.x * 16 + i]);
   sha1_block(st, M);
   for (int i = 0; i < 5; i++) out[threadIdx.x * 5 + i] = st[i];
+}
+__global__ void p_sha512(const uint32_t* in, uint32_t* out) {
+  uint64_t M[16], st[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                           0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+  for (int i = 0; i < 16; i++)
+    M[i] = sha_pack64(sha_bswap(in[threadIdx.x * 32 + 2 * i + 1]), sha_bswap(in[threadIdx.x * 32 + 2 * i]));
+  sha512_block(st, M);
+  for (int i = 0; i < 8; i++) {
+    out[threadIdx.x * 16 + 2 * i] = (uint32_t)(st[i] >> 32);
+    out[threadIdx.x * 16 + 2 * i + 1] = (uint32_t)st[i];
+  }
 }
 __global__ void p_sha256(const uint32_t* in, uint32_t* out) {
   uint32_t M[16], st[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu,
@@ -108,7 +120,8 @@ def main():
     open(p, "w").write(PROBE)
     t = asm(p)
     res = {"md5_block": mix(func_ops(t, "_Z5p_md5PKjPj")), "md4_block": mix(func_ops(t, "_Z5p_md4PKjPj")),
-           "sha1_block": mix(func_ops(t, "_Z6p_sha1PKjPj")), "sha256_block": mix(func_ops(t, "_Z8p_sha256PKjPj"))}
+           "sha1_block": mix(func_ops(t, "_Z6p_sha1PKjPj")), "sha256_block": mix(func_ops(t, "_Z8p_sha256PKjPj")),
+           "sha512_block": mix(func_ops(t, "_Z8p_sha512PKjPj"))}
     k = asm(os.path.join(CSRC, "a5x_kernels.hip"))
     res["k_expand_fast_md5 (static, whole kernel)"] = mix(func_ops(k, "_Z17k_expand_fast_md57ExpArgs"))
     res["k_expand_fast_ntlm (static, whole kernel)"] = mix(func_ops(k, "_Z18k_expand_fast_ntlm7ExpArgs"))

@@ -1,6 +1,7 @@
 // mb_valu.hip -- SIMD issue cost of the integer VALU instructions the fused digests are made of
 // (MD5 / MD4 rounds: v_add3_u32, v_bitop3_b32, v_alignbit_b32, v_bfi_b32, v_alignbit_b32, ...; the expansion: v_perm_b32,
-// v_alignbyte_b32, v_lshl_or_b32), at 1 / 2 / 4 / 8 waves per SIMD.
+// v_alignbyte_b32, v_lshl_or_b32; the 64-bit adds of SHA-512: v_lshl_add_u64 against a v_add_co_u32 +
+// v_addc_co_u32 pair), at 1 / 2 / 4 / 8 waves per SIMD.
 //
 // Every instruction is an inline-asm statement (the opcode cannot be changed or folded), its
 // operands come from memory (no compile-time values) and every chain ends in the output, so no
@@ -69,6 +70,46 @@ __global__ void __launch_bounds__(256) k_valu(const u32* in, u32* out, unsigned 
   if ((threadIdx.x & 63) == 0) ticks[t / 64] = t1 - t0;
 }
 
+// 64-bit adds on register pairs: OP 0 = v_lshl_add_u64 (what the compiler emits for x + y), OP 1 = the
+// carry pair v_add_co_u32 + v_addc_co_u32 through VCC (2 instructions per step)
+typedef unsigned long long u64;
+template <int OP>
+__device__ __forceinline__ u64 op64(u64 x, u64 y) {
+  u64 r;
+  if constexpr (OP == 0) {
+    asm volatile("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(r) : "v"(x), "v"(y));
+  } else {
+    u32 lo, hi;
+    asm volatile("v_add_co_u32 %0, vcc, %2, %4\n\tv_addc_co_u32 %1, vcc, %3, %5, vcc"
+                 : "=&v"(lo), "=v"(hi)
+                 : "v"((u32)x), "v"((u32)(x >> 32)), "v"((u32)y), "v"((u32)(y >> 32))
+                 : "vcc");
+    r = (u64)lo | ((u64)hi << 32);
+  }
+  return r;
+}
+
+template <int OP>
+__global__ void __launch_bounds__(256) k_valu64(const u32* in, u32* out, unsigned long long* ticks, int iters) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  const u64* in2 = (const u64*)in;
+  u64 a = in2[t & 511], b = in2[(t + 1) & 511], c = in2[(t + 2) & 511], d = in2[(t + 3) & 511];
+  u64 e = in2[(t + 4) & 511], f = in2[(t + 5) & 511], g = in2[(t + 6) & 511], h = in2[(t + 7) & 511];
+  __builtin_amdgcn_s_waitcnt(0);
+  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+  for (int i = 0; i < iters; i++) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      a = op64<OP>(a, b); b = op64<OP>(b, c); c = op64<OP>(c, d); d = op64<OP>(d, e);
+      e = op64<OP>(e, f); f = op64<OP>(f, g); g = op64<OP>(g, h); h = op64<OP>(h, a);
+    }
+  }
+  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+  const u64 x = a ^ b ^ c ^ d ^ e ^ f ^ g ^ h;
+  out[t] = (u32)x ^ (u32)(x >> 32);
+  if ((threadIdx.x & 63) == 0) ticks[t / 64] = t1 - t0;
+}
+
 typedef void (*KFn)(const u32*, u32*, unsigned long long*, int);
 int main() {
   u32 *in, *out;
@@ -83,16 +124,17 @@ int main() {
   const char* names[] = {"v_add_u32 (VOP2)", "v_xor_b32 (VOP2)", "v_add3_u32", "v_xad_u32", "v_bfi_b32", "v_alignbit_b32",
                          "v_perm_b32", "v_alignbyte_b32", "v_lshl_or_b32", "v_lshl_add_u32", "v_mul_hi_u32",
                          "v_cmp + v_cndmask (2 instr)", "v_bitop3_b32 (CDNA4)", "v_add_u32_e64", "v_lshlrev_b32_e64",
-                         "v_add3_u32 (2 VGPR + imm)"};
+                         "v_add3_u32 (2 VGPR + imm)", "v_lshl_add_u64", "v_add_co + v_addc_co (2 instr)"};
   KFn fns[] = {k_valu<0>, k_valu<1>, k_valu<2>, k_valu<3>, k_valu<4>, k_valu<5>, k_valu<6>, k_valu<7>,
-               k_valu<8>, k_valu<9>, k_valu<10>, k_valu<11>, k_valu<12>, k_valu<13>, k_valu<14>, k_valu<15>};
+               k_valu<8>, k_valu<9>, k_valu<10>, k_valu<11>, k_valu<12>, k_valu<13>, k_valu<14>, k_valu<15>,
+               k_valu64<0>, k_valu64<1>};
   const int iters = 4000;
   hipEvent_t e0, e1;
   CHK(hipEventCreate(&e0));
   CHK(hipEventCreate(&e1));
   printf("%-28s %s\n", "instruction", "SIMD cycles per wave-instruction at 1 / 2 / 4 / 8 waves per SIMD");
   double fclk = 0;
-  for (int o = 0; o < 16; o++) {
+  for (int o = 0; o < 18; o++) {
     printf("%-28s", names[o]);
     for (int wps : {1, 2, 4, 8}) {
       const int blocks = 256 * wps;  // 256-thread blocks: one wave per SIMD each
@@ -110,7 +152,7 @@ int main() {
         for (auto v : tk) mean += (double)v;
         mean /= tk.size();
         if (o == 0 && wps == 1 && rep == 2) fclk = mean / (ms * 1e-3);
-        const double instr = (double)iters * 16 * 8 * (o == 11 ? 2 : 1);
+        const double instr = (double)iters * 16 * 8 * (o == 11 || o == 17 ? 2 : 1);
         const double t = ms * 1e-3;
         best = t < best ? t : best;
         if (rep == 2 && fclk > 0) best = best * fclk / (instr * wps);
