@@ -34,6 +34,8 @@ EXPORTS = (
     "a5x_stream_reserve",
     "a5x_set_rules", "a5x_load_rules_file", "a5x_rule_count", "a5x_hit_rules", "a5x_rules_last",
     "a5x_format_hits_rules", "a5x_digest_lines_rules_device", "a5x_debug_apply_rule",
+    "a5x_set_salted_targets", "a5x_load_salted_hashes", "a5x_salt_count", "a5x_salt_get", "a5x_hit_salts",
+    "a5x_salts_last", "a5x_format_hits_salted", "a5x_digest_lines_salted_device", "a5x_debug_digest_salted",
 )
 
 
@@ -135,6 +137,16 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     L.a5x_format_hits_rules.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, SINK, vp]
     L.a5x_digest_lines_rules_device.argtypes = [vp, i, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
     L.a5x_debug_apply_rule.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz)]
+    L.a5x_set_salted_targets.argtypes = [vp, i, i, vp, u64, vp, vp]
+    L.a5x_load_salted_hashes.argtypes = [vp, i, i, ctypes.c_char_p, sz, i, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                         ctypes.POINTER(u64)]
+    L.a5x_salt_count.argtypes = [vp]
+    L.a5x_salt_get.argtypes = [vp, u32, vp, sz, ctypes.POINTER(sz)]
+    L.a5x_hit_salts.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.a5x_salts_last.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.a5x_format_hits_salted.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, i, SINK, vp]
+    L.a5x_digest_lines_salted_device.argtypes = [vp, i, i, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
+    L.a5x_debug_digest_salted.argtypes = [i, i, ctypes.c_char_p, sz, ctypes.c_char_p, sz, vp, sz]
     _lib = L
     return L
 

@@ -6,7 +6,8 @@
 //
 //   a5x_generator <dict-file> -t <table> [-t <table> ...] [-m N] [-x N]
 //                 [--threads N] [-s] [-r] [--device N]
-//                 [--hashes <file> [--algo md5|ntlm|sha1|sha224|sha256|sha384|sha512] [--rules <file>]]
+//                 [--hashes <file> [--algo md5|ntlm|sha1|sha224|sha256|sha384|sha512] [--rules <file>]
+//                                  [--salted=pass.salt|salt.pass [--hex-salt]]]
 //                 [--skip N] [--limit N] [--keyspace]
 //
 // --hashes (a5x extension): instead of printing the candidates for a
@@ -14,6 +15,13 @@
 // the hex digests of <file> and print what hashcat would report, "hash:plain" (plains
 // that hashcat would hexify as $HEX[...]), each target once, at its first candidate in
 // stream order (README.MD:74-106, :168).
+//
+// --salted (with --hashes): <file> holds "hash:salt" lines and the digest is over candidate +
+// salt (pass.salt; hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710) or salt + candidate
+// (salt.pass; -m 20 / 120 / 1320 / 1420 / 10820 / 1720); --algo given as one of those mode
+// numbers implies it.  Every (hash, salt) target is reported once, at its first candidate in
+// stream order, as "hash:salt:plain" (--hex-salt: the salts are hex in the file and in the
+// output).  Without --salted a ":suffix" after a hash is ignored, as before.
 //
 // --skip / --limit / --keyspace (a5x extension, SURVEY §5 checkpoint / resume): the
 // stream's candidate order does not depend on batching (a word's candidates are
@@ -61,6 +69,11 @@ static void usage(FILE* f) {
           "      --algo=md5                    Digest of --hashes: md5 (hashcat -m 0), ntlm (-m 1000),\n"
           "                                    sha1 (-m 100), sha224 (-m 1300), sha256 (-m 1400),\n"
           "                                    sha384 (-m 10800) or sha512 (-m 1700); a name or the -m number\n"
+          "      --salted=ORDER                With --hashes: FILE holds hash:salt lines; ORDER is pass.salt\n"
+          "                                    (hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710) or salt.pass\n"
+          "                                    (-m 20 / 120 / 1320 / 1420 / 10820 / 1720); --algo also takes\n"
+          "                                    those mode numbers, which imply the order\n"
+          "      --hex-salt                    With --salted: the salts of FILE are hex-encoded\n"
           "      --skip=0                      Resume: start at candidate N of the stream (a5x extension)\n"
           "      --limit=N                     Print at most N candidates (a5x extension)\n"
           "      --keyspace                    Print the number of candidates and exit (a5x extension)\n");
@@ -212,6 +225,25 @@ static int load_targets(a5x_ctx* ctx, const char* path, int algo) {
   return a5x_set_targets(ctx, algo, dig.empty() ? nullptr : dig.data(), dig.size() / (size_t)dsz);
 }
 
+// --salted: the whole "hash:salt" file through a5x_load_salted_hashes
+static int load_salted_targets(a5x_ctx* ctx, const char* path, int algo, int order, bool hex_salt) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return A5X_E_IO;
+  std::vector<uint8_t> text;
+  uint8_t buf[1 << 16];
+  size_t n;
+  while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.insert(text.end(), buf, buf + n);
+  const bool bad = ferror(f) != 0;
+  fclose(f);
+  if (bad) return A5X_E_IO;
+  uint64_t nt = 0, ns = 0, nsk = 0;
+  const int rc = a5x_load_salted_hashes(ctx, algo, order, text.data(), text.size(), hex_salt ? 1 : 0, &nt, &ns, &nsk);
+  if (rc == 0)
+    fprintf(stderr, "a5_generator: salted: %llu target(s), %llu distinct salt(s), %llu line(s) skipped (not hash:salt)\n",
+            (unsigned long long)nt, (unsigned long long)ns, (unsigned long long)nsk);
+  return rc;
+}
+
 static bool parse_u64(const char* s, uint64_t* out) {
   char* e;
   errno = 0;
@@ -290,7 +322,9 @@ int main(int argc, char** argv) {
   std::vector<std::string> tables;
   std::string dict;
   int tmin = 0, tmax = 15, threads = -1, device = 0, algo = A5X_ALGO_MD5;
-  std::string hashes, rules;
+  std::string hashes, rules, salted;
+  int mode_order = -1;  // the order a hashcat mode number given as --algo implies
+  bool hex_salt = false;
   bool suball = false, rev = false, keyspace_only = false, cursor = false;
   uint64_t skip = 0, limit = ~0ull;
   auto need = [&](int& i, const char* flag) -> const char* {
@@ -347,10 +381,24 @@ int main(int argc, char** argv) {
       else if (v == "sha224" || v == "1300") algo = A5X_ALGO_SHA224;
       else if (v == "sha384" || v == "10800") algo = A5X_ALGO_SHA384;
       else if (v == "sha512" || v == "1700") algo = A5X_ALGO_SHA512;
+      else if (v == "10" || v == "20") { algo = A5X_ALGO_MD5; mode_order = v == "20"; }
+      else if (v == "110" || v == "120") { algo = A5X_ALGO_SHA1; mode_order = v == "120"; }
+      else if (v == "1310" || v == "1320") { algo = A5X_ALGO_SHA224; mode_order = v == "1320"; }
+      else if (v == "1410" || v == "1420") { algo = A5X_ALGO_SHA256; mode_order = v == "1420"; }
+      else if (v == "1710" || v == "1720") { algo = A5X_ALGO_SHA512; mode_order = v == "1720"; }
+      else if (v == "10810" || v == "10820") { algo = A5X_ALGO_SHA384; mode_order = v == "10820"; }
       else {
         fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1, sha224, sha256, sha384 or sha512\n");
         return 80;
       }
+    } else if (s.rfind("--salted", 0) == 0) {
+      salted = val_of("--salted");
+      if (salted != "pass.salt" && salted != "salt.pass") {
+        fprintf(stderr, "a5_generator: error: --salted: pass.salt or salt.pass\n");
+        return 80;
+      }
+    } else if (s == "--hex-salt") {
+      hex_salt = true;
     } else if (s.rfind("--skip", 0) == 0) {
       if (!parse_u64(val_of("--skip"), &skip)) { fprintf(stderr, "a5_generator: error: --skip: bad count\n"); return 80; }
       cursor = true;
@@ -388,6 +436,31 @@ int main(int argc, char** argv) {
   setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
   if (!rules.empty() && hashes.empty()) {
     fprintf(stderr, "a5_generator: error: --rules applies to the digest + lookup stage: it needs --hashes\n");
+    return 80;
+  }
+  int order = -1;  // >= 0: the --hashes list is salted
+  if (!salted.empty()) order = salted == "salt.pass";
+  if (mode_order >= 0) {
+    if (order >= 0 && order != mode_order) {
+      fprintf(stderr, "a5_generator: error: --salted=%s contradicts the hashcat mode given as --algo\n", salted.c_str());
+      return 80;
+    }
+    order = mode_order;
+  }
+  if ((order >= 0 || hex_salt) && hashes.empty()) {
+    fprintf(stderr, "a5_generator: error: --salted / --hex-salt / a salted hashcat mode apply to --hashes\n");
+    return 80;
+  }
+  if (hex_salt && order < 0) {
+    fprintf(stderr, "a5_generator: error: --hex-salt needs --salted\n");
+    return 80;
+  }
+  if (order >= 0 && !rules.empty()) {
+    fprintf(stderr, "a5_generator: error: --salted with --rules: rules and salts together are not supported\n");
+    return 80;
+  }
+  if (order >= 0 && algo == A5X_ALGO_NTLM) {
+    fprintf(stderr, "a5_generator: error: --salted with --algo ntlm: NTLM has no salted mode\n");
     return 80;
   }
   if (!hashes.empty() && (cursor || keyspace_only)) {
@@ -523,7 +596,7 @@ int main(int argc, char** argv) {
   }
   FILE* f = fopen(dict.c_str(), "rb");
   if (!f) { perror(dict.c_str()); a5x_destroy(ctx); return 1; }
-  if ((rc = load_targets(ctx, hashes.c_str(), algo))) {
+  if ((rc = order >= 0 ? load_salted_targets(ctx, hashes.c_str(), algo, order, hex_salt) : load_targets(ctx, hashes.c_str(), algo))) {
     fprintf(stderr, "a5_generator: %s\n", rc == A5X_E_IO ? "cannot read --hashes file" : a5x_last_error(ctx));
     a5x_destroy(ctx);
     fclose(f);
@@ -547,6 +620,8 @@ int main(int argc, char** argv) {
     }
   }
   const bool ruled = !rules.empty();
+  const bool with_salts = order >= 0;
+  uint64_t skipped_pairs = 0;
   DictStream ds(f, chunk);
   std::vector<uint8_t> words;
   std::vector<uint64_t> sub;
@@ -568,6 +643,11 @@ int main(int argc, char** argv) {
       if ((rc = a5x_hit_rules(ctx, hrule.data(), hrule.size(), &nr)) || (rc = a5x_rules_last(ctx, nullptr, &rej))) break;
       rejected += rej;
     }
+    if (with_salts) {  // (hrule carries each hit's salt index: a list is ruled or salted, never both)
+      uint64_t ns = 0, skp = 0;
+      if ((rc = a5x_hit_salts(ctx, hrule.data(), hrule.size(), &ns)) || (rc = a5x_salts_last(ctx, nullptr, &skp))) break;
+      skipped_pairs += skp;
+    }
     // stream order (then rule order), then the first candidate of each digest
     std::vector<uint64_t> ord(nh);
     for (uint64_t h = 0; h < nh; h++) ord[h] = h;
@@ -583,13 +663,18 @@ int main(int argc, char** argv) {
       uint8_t full[64];
       size_t fl = 0;
       if ((rc = a5x_hit_digest(ctx, &hits[h], full, sizeof full, &fl))) break;
-      if (cracked.insert(std::string((const char*)full, fl)).second) {
+      std::string key((const char*)full, fl);
+      if (with_salts) key.append((const char*)&hrule[h], 4);  // a target is a (hash, salt) pair
+      if (cracked.insert(key).second) {
         first.push_back(hits[h]);
         first_rule.push_back(hrule[h]);
       }
     }
     if (rc) break;
-    if (ruled)
+    if (with_salts)
+      rc = a5x_format_hits_salted(ctx, wb, sub.data(), nb, mode, tmin, tmax, first.data(), first.size(),
+                                  first_rule.data(), hex_salt ? 1 : 0, sink_stdout, nullptr);
+    else if (ruled)
       rc = a5x_format_hits_rules(ctx, wb, sub.data(), nb, mode, tmin, tmax, first.data(), first.size(),
                                  first_rule.data(), sink_stdout, nullptr);
     else
@@ -599,6 +684,9 @@ int main(int argc, char** argv) {
   if (ruled)
     fprintf(stderr, "a5_generator: rules: %llu candidate(s) longer than 128 bytes rejected\n",
             (unsigned long long)rejected);
+  if (with_salts)
+    fprintf(stderr, "a5_generator: salted: %llu (candidate, salt) pair(s) longer than 128 bytes skipped\n",
+            (unsigned long long)skipped_pairs);
   fclose(f);
   fflush(stdout);
   if (rc) fprintf(stderr, "a5_generator: %s\n", a5x_last_error(ctx));

@@ -31,6 +31,7 @@
 #include "a5x_launch.h"
 #include "a5x_md.h"
 #include "a5x_rules.h"
+#include "a5x_salt.h"
 #include "a5x_sha.h"
 
 namespace {
@@ -142,6 +143,20 @@ struct a5x_ctx {
   DevBuf<unsigned long long> r_counter;
   std::vector<uint32_t> r_hit_rule;
   uint64_t r_rejected = 0, r_hashed = 0;
+  // salted target lists (a5x_salt.hip): the set's order, its distinct salts in first-
+  // appearance order (bytes + n + 1 offsets), the salt records sorted by length (host copy +
+  // device copy), and of the latest digest call: each copied hit's salt index, the (candidate,
+  // salt) pairs hashed and skipped.  The pair counter on the device is r_counter: a context
+  // holds rules or salts, never both.
+  bool salted = false;
+  int s_order = 0;
+  std::vector<uint8_t> s_bytes;
+  std::vector<uint64_t> s_off;
+  std::vector<uint32_t> s_recs;
+  uint32_t n_salts = 0;
+  DevBuf<uint32_t> s_table, dg_hit_salt;
+  std::vector<uint32_t> s_hit_salt;
+  uint64_t s_hashed = 0, s_skipped = 0;
 
   DevBuf<uint64_t> count, bytes, cand_off, byte_off, scan_tmp, locate;
   DevBuf<uint32_t> flags, defer, chunk_w0, slow_list, big_list, roff, cplx;
@@ -1304,7 +1319,8 @@ struct TargetSet {
   std::vector<uint8_t> full;
   bool shared = false;  // two digests share their first 16 bytes
 };
-void build_target_set(uint32_t W, const uint8_t* dig, uint64_t n, TargetSet& T) {
+// (full_src: the digests the host copy is made of when dig holds masked keys, a5x_set_salted_targets)
+void build_target_set(uint32_t W, const uint8_t* dig, uint64_t n, TargetSet& T, const uint8_t* full_src = nullptr) {
   // prefilter: >= 64 bits per target (false-positive rate <= 1/64), table: load <= 1/2
   uint32_t bm_log2 = 16;
   const uint32_t TW = W / 4 - 4;  // tail words
@@ -1353,7 +1369,8 @@ void build_target_set(uint32_t W, const uint8_t* dig, uint64_t n, TargetSet& T) 
   full.clear();
   bool shared = false;
   if (TW) {
-    full.assign(dig, dig + (uint64_t)W * n);
+    const uint8_t* fs = full_src ? full_src : dig;
+    full.assign(fs, fs + (uint64_t)W * n);
     switch (W) {
       case 20: sort_unique_digests<20>(full); break;
       case 28: sort_unique_digests<28>(full); break;
@@ -1467,6 +1484,12 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   if (ruled) allow_fused = false;
   c->r_hit_rule.clear();
   c->r_rejected = c->r_hashed = 0;
+  // a salted target set: the two-pass range loop in every mode, k_salt_stream in that place
+  // (a5x_set_rules / a5x_set_salted_targets refuse the two together)
+  const bool salted = c->salted;
+  if (salted) allow_fused = false;
+  c->s_hit_salt.clear();
+  c->s_hashed = c->s_skipped = 0;
   Job J;
   job_open(c, J, d_words, d_woff, nw, mode, mn, mx, st);
   J.lengths = mode == A5X_MODE_DEFAULT || !allow_fused;  // the fused -r / -s digest needs no layout
@@ -1667,6 +1690,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   const uint32_t HT = a5x_hit_tail_stride(c->t_algo);  // tail words the kernels record per hit
   if (wide && (rc = grow(c, c->dg_hit_tail, (uint64_t)HT * dev_hits))) return rc;
   if (ruled && ((rc = grow(c, c->dg_hit_rule, dev_hits)) || (rc = grow(c, c->r_counter, 2)))) return rc;
+  if (salted && ((rc = grow(c, c->dg_hit_salt, dev_hits)) || (rc = grow(c, c->r_counter, 2)))) return rc;
   std::vector<uint32_t> htail;  // wide: the range's hit tails
   a5x_stats total;
   memset(&total, 0, sizeof total);
@@ -1685,13 +1709,13 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
     A5xDigLaunch D = dig_launch(c);
     D.out = c->dg_scratch.p;
     D.nbytes = R.b1 - R.b0;
-    const uint64_t nblk = ruled ? a5x_rules_blocks(D.nbytes) : a5x_digest_blocks(D.nbytes, D.algo);
+    const uint64_t nblk = ruled ? a5x_rules_blocks(D.nbytes) : salted ? a5x_salt_blocks(D.nbytes) : a5x_digest_blocks(D.nbytes, D.algo);
     if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
         (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)))
       return rc;
     D.blk_cnt = c->dg_blk_cnt.p;
     uint64_t nh = 0;
-    unsigned long long rej = 0;  // ruled: the range's lines longer than A5X_RULE_LMAX
+    unsigned long long rej = 0;  // ruled: the range's lines longer than A5X_RULE_LMAX; salted: its skipped pairs
     {
       float me = 0;  // the range's expansion, once (a retry below re-runs only the digest)
       HIPCHK(c, hipEventSynchronize(c->ev[2]));
@@ -1704,9 +1728,19 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       D.hit_cap = (uint32_t)dev_hits;
       D.nhits = c->d_scalars + 8;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 8, 0, 4, J.st));
-      if (ruled) HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, J.st));
+      if (ruled || salted) HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, J.st));
       HIPCHK(c, hipEventRecord(c->dev_ev[0], J.st));
-      if (ruled) {
+      if (salted) {
+        A5xSaltLaunch SL;
+        SL.d = D;
+        SL.salts = c->s_table.p;
+        SL.nsalts = c->n_salts;
+        SL.order = c->s_order;
+        SL.hit_salt = c->dg_hit_salt.p;
+        SL.skipped = c->r_counter.p;
+        // (an empty salted set has no salt to hash under: no launch, no hit)
+        if (c->n_salts) HIPCHK(c, a5x_launch_salt_stream(SL, 0, (uint32_t)std::max(1, c->cus), J.st));
+      } else if (ruled) {
         A5xRuleLaunch RL;
         RL.d = D;
         RL.rules = c->r_table.p;
@@ -1719,7 +1753,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       }
       HIPCHK(c, hipEventRecord(c->dev_ev[1], J.st));
       HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, J.st));
-      if (ruled) HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, J.st));
+      if (ruled || salted) HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, J.st));
       HIPCHK(c, hipStreamSynchronize(J.st));
       float md = 0;
       HIPCHK(c, hipEventElapsedTime(&md, c->dev_ev[0], c->dev_ev[1]));
@@ -1732,7 +1766,14 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
       if (wide && (rc = grow(c, c->dg_hit_tail, (uint64_t)HT * dev_hits))) return rc;
       if (ruled && (rc = grow(c, c->dg_hit_rule, dev_hits))) return rc;
+      if (salted && (rc = grow(c, c->dg_hit_salt, dev_hits))) return rc;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 2, 0, 4, J.st));
+    }
+    if (salted) {
+      const uint64_t pairs = (R.ce - R.cb) * c->n_salts;
+      if (rej > pairs) return fail(c, A5X_E_HIP, "more skipped pairs than the range has");
+      c->s_skipped += rej;
+      c->s_hashed += pairs - rej;
     }
     if (ruled) {
       if (rej > R.ce - R.cb) return fail(c, A5X_E_HIP, "more rejected lines than the range has candidates");
@@ -1755,6 +1796,10 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       if (take && ruled) {
         c->r_hit_rule.resize(copied + take);
         HIPCHK(c, hipMemcpyAsync(c->r_hit_rule.data() + copied, c->dg_hit_rule.p, take * 4, hipMemcpyDeviceToHost, J.st));
+      }
+      if (take && salted) {
+        c->s_hit_salt.resize(copied + take);
+        HIPCHK(c, hipMemcpyAsync(c->s_hit_salt.data() + copied, c->dg_hit_salt.p, take * 4, hipMemcpyDeviceToHost, J.st));
       }
       HIPCHK(c, hipStreamSynchronize(J.st));
       if (take && c->t_shared_prefix)  // (which of the targets sharing a prefix each hit matched: a5x_hit_digest)
@@ -1878,6 +1923,7 @@ void a5x_destroy(a5x_ctx* c) {
   release(c->dg_cand_off); release(c->dg_byte_off); release(c->dg_hits);
   release(c->t_tails); release(c->t_ztails); release(c->dg_hit_tail);
   release(c->r_table); release(c->dg_hit_rule); release(c->r_counter);
+  release(c->s_table); release(c->dg_hit_salt);
   release(c->hy_list); release(c->hy_lens); release(c->hy_off); release(c->hy_words);
   for (auto& e : c->dev_ev)
     if (e) (void)hipEventDestroy(e);
@@ -2501,15 +2547,20 @@ int a5x_debug_plan_sizes(a5x_ctx* c, const uint8_t* word, size_t len, uint32_t* 
   return A5X_OK;
 }
 
-int a5x_set_targets(a5x_ctx* c, int algo, const uint8_t* dig, uint64_t n) {
-  if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
-  if (!c || (n && !dig)) return A5X_E_ARG;
-  const uint32_t W = algo_size(algo);  // digest bytes
-  if (!W) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
-  const uint32_t TW = W / 4 - 4;       // tail words
-  HIPCHK(c, hipSetDevice(c->device));
-  TargetSet T;
-  build_target_set(W, dig, n, T);
+// the context's salted state dropped: the target set (if any) is an unsalted one
+static void clear_salts(a5x_ctx* c) {
+  c->salted = false;
+  c->n_salts = 0;
+  c->s_bytes.clear();
+  c->s_off.clear();
+  c->s_recs.clear();
+  c->s_hit_salt.clear();
+  c->s_hashed = c->s_skipped = 0;
+}
+
+// the built target set into the context's device buffers (a5x_set_targets, a5x_set_salted_targets)
+static int upload_target_set(a5x_ctx* c, int algo, uint64_t n, TargetSet& T) {
+  const uint32_t TW = algo_size(algo) / 4 - 4;  // tail words
   int rc;
   if ((rc = grow(c, c->t_bitmap, T.bm.size())) || (rc = grow(c, c->t_table, T.tab.size()))) return rc;
   if (TW && ((rc = grow(c, c->t_tails, T.tails.size())) || (rc = grow(c, c->t_ztails, T.ztails.size() + 1)))) return rc;
@@ -2528,6 +2579,345 @@ int a5x_set_targets(a5x_ctx* c, int algo, const uint8_t* dig, uint64_t n) {
   c->t_bm_log2 = T.bm_log2;
   c->t_tmask = T.tmask;
   c->t_has_zero = T.has_zero;
+  return A5X_OK;
+}
+
+int a5x_set_targets(a5x_ctx* c, int algo, const uint8_t* dig, uint64_t n) {
+  if (c && c->device < 0) {
+    clear_salts(c);  // (a host-only context keeps a salted set's host copy: dropped, as on a device context)
+    return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
+  }
+  if (!c || (n && !dig)) return A5X_E_ARG;
+  const uint32_t W = algo_size(algo);  // digest bytes
+  if (!W) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
+  HIPCHK(c, hipSetDevice(c->device));
+  TargetSet T;
+  build_target_set(W, dig, n, T);
+  const int rc = upload_target_set(c, algo, n, T);
+  if (rc == A5X_OK) clear_salts(c);  // the set is unsalted again
+  return rc;
+}
+
+// ---- salted target lists (a5x_salt.h, a5x_salt.hip) ------------------------------
+int a5x_set_salted_targets(a5x_ctx* c, int algo, int order, const uint8_t* dig, uint64_t n, const uint8_t* salt_bytes,
+                           const uint64_t* salt_off) {
+  if (!c) return A5X_E_ARG;
+  const uint32_t W = algo_size(algo);  // digest bytes
+  if (!W || algo == A5X_ALGO_NTLM) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
+  if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS)
+    return fail(c, A5X_E_ARG, "salt order %d: 0 is pass.salt, 1 is salt.pass", order);
+  if (n && (!dig || !salt_off)) return fail(c, A5X_E_ARG, "null digests or salt offsets");
+  for (uint64_t i = 0; i < n; i++) {
+    if (salt_off[i + 1] < salt_off[i]) return fail(c, A5X_E_ARG, "salt offsets of target %llu decrease", (unsigned long long)i);
+    if (salt_off[i + 1] - salt_off[i] > A5X_SALT_MAX)
+      return fail(c, A5X_E_ARG, "salt of target %llu has %llu bytes, the limit is %u", (unsigned long long)i,
+                  (unsigned long long)(salt_off[i + 1] - salt_off[i]), A5X_SALT_MAX);
+    if (salt_off[i + 1] > salt_off[i] && !salt_bytes) return fail(c, A5X_E_ARG, "null salt bytes");
+  }
+  if (c->n_rules)
+    return fail(c, A5X_E_UNSUPPORTED, "rules and salted targets together are not supported: %u rules are loaded (clear them first)",
+                c->n_rules);
+  // distinct salts, indexed by first appearance; every target's salt index
+  std::unordered_map<std::string, uint32_t> index;
+  std::vector<uint8_t> sb;
+  std::vector<uint64_t> so(1, 0);
+  std::vector<uint32_t> tidx(n);
+  for (uint64_t i = 0; i < n; i++) {
+    const size_t sl = (size_t)(salt_off[i + 1] - salt_off[i]);
+    std::string s(sl ? (const char*)salt_bytes + salt_off[i] : "", sl);
+    auto it = index.find(s);
+    if (it == index.end()) {
+      it = index.emplace(s, (uint32_t)(so.size() - 1)).first;
+      sb.insert(sb.end(), s.begin(), s.end());
+      so.push_back(sb.size());
+    }
+    tidx[i] = it->second;
+  }
+  const uint32_t S = (uint32_t)(so.size() - 1);
+  // the device salt table: one record per salt, sorted by length (salt.pass copies the
+  // candidate once per run of equal lengths), the public index kept in the record
+  std::vector<uint32_t> ord(S);
+  for (uint32_t i = 0; i < S; i++) ord[i] = i;
+  std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return so[x + 1] - so[x] < so[y + 1] - so[y]; });
+  std::vector<uint32_t> recs((size_t)S * A5X_SALT_STRIDE, 0u);
+  for (uint32_t k = 0; k < S; k++) {
+    uint32_t* r = &recs[(size_t)k * A5X_SALT_STRIDE];
+    const uint32_t i = ord[k], sl = (uint32_t)(so[i + 1] - so[i]);
+    r[A5X_SALT_R_LEN] = sl;
+    r[A5X_SALT_R_INDEX] = i;
+    salt_mask(i, r + A5X_SALT_R_MASK);
+    if (sl) memcpy(r + A5X_SALT_R_BYTES, sb.data() + so[i], sl);
+  }
+  if (c->device >= 0) {
+    // the target set keyed on the masked digests: the first 16 bytes XOR the salt's mask
+    std::vector<uint8_t> md(dig, dig + (size_t)W * n);
+    for (uint64_t i = 0; i < n; i++) {
+      uint32_t m[4], d[4];
+      salt_mask(tidx[i], m);
+      memcpy(d, &md[(size_t)W * i], 16);
+      for (int k = 0; k < 4; k++) d[k] ^= m[k];
+      memcpy(&md[(size_t)W * i], d, 16);
+    }
+    auto upload = [&]() -> int {
+      int rc;
+      HIPCHK(c, hipSetDevice(c->device));
+      HIPCHK(c, hipStreamSynchronize(c->stream));  // (no kernel of an earlier call still reads the tables)
+      TargetSet T;
+      build_target_set(W, md.data(), n, T, dig);
+      if ((rc = upload_target_set(c, algo, n, T))) return rc;
+      if ((rc = grow(c, c->s_table, recs.size() + 1))) return rc;
+      if (S) HIPCHK(c, hipMemcpy(c->s_table.p, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
+      return A5X_OK;
+    };
+    const int rc = upload();
+    if (rc) {  // a half-replaced set (masked table without its salts, or the reverse) is no set
+      c->t_algo = -1;
+      clear_salts(c);
+      return rc;
+    }
+  } else {
+    c->t_algo = algo;
+    c->n_targets = n;
+  }
+  c->salted = true;
+  c->s_order = order;
+  c->n_salts = S;
+  c->s_bytes.swap(sb);
+  c->s_off.swap(so);
+  c->s_recs.swap(recs);
+  c->s_hit_salt.clear();
+  c->s_hashed = c->s_skipped = 0;
+  return A5X_OK;
+}
+
+int a5x_load_salted_hashes(a5x_ctx* c, int algo, int order, const uint8_t* text, size_t len, int hex_salt,
+                           uint64_t* n_targets, uint64_t* n_salts, uint64_t* n_skipped) {
+  if (!c || (len && !text)) return A5X_E_ARG;
+  const uint32_t W = algo_size(algo);
+  if (!W || algo == A5X_ALGO_NTLM) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
+  auto hexv = [](uint8_t ch) -> int {
+    return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1;
+  };
+  std::vector<uint8_t> dig, sb;
+  std::vector<uint64_t> so(1, 0);
+  uint64_t bad = 0;
+  for (size_t p = 0; p < len;) {
+    size_t e = p;
+    while (e < len && text[e] != '\n') e++;
+    size_t n = e - p;
+    const uint8_t* l = text + p;
+    p = e + 1;
+    if (n && l[n - 1] == '\r') n--;
+    if (!n) continue;  // (an empty line is no target and no error)
+    uint8_t d[64];
+    bool ok = n > 2u * W && l[2u * W] == ':';  // the digest, then the first ':'
+    for (uint32_t k = 0; ok && k < 2u * W; k++) {
+      const int v = hexv(l[k]);
+      if (v < 0) ok = false;
+      else if (k & 1u) d[k / 2] |= (uint8_t)v;
+      else d[k / 2] = (uint8_t)(v << 4);
+    }
+    const uint8_t* s = l + 2u * W + 1u;
+    size_t sl = ok ? n - (2u * W + 1u) : 0;
+    uint8_t raw[A5X_SALT_MAX];
+    if (ok && hex_salt) {
+      ok = (sl & 1u) == 0 && sl / 2 <= A5X_SALT_MAX;
+      for (size_t k = 0; ok && k < sl; k += 2) {
+        const int hi = hexv(s[k]), lo = hexv(s[k + 1]);
+        if (hi < 0 || lo < 0) ok = false;
+        else raw[k / 2] = (uint8_t)(hi << 4 | lo);
+      }
+      s = raw;
+      sl /= 2;
+    }
+    if (ok && sl > A5X_SALT_MAX) ok = false;
+    if (!ok) { bad++; continue; }
+    dig.insert(dig.end(), d, d + W);
+    sb.insert(sb.end(), s, s + sl);
+    so.push_back(sb.size());
+  }
+  const uint64_t n = so.size() - 1;
+  if (n_skipped) *n_skipped = bad;
+  const int rc = a5x_set_salted_targets(c, algo, order, dig.data(), n, sb.data(), so.data());
+  if (rc) return rc;
+  if (n_targets) *n_targets = n;
+  if (n_salts) *n_salts = c->n_salts;
+  return A5X_OK;
+}
+
+int a5x_salt_count(const a5x_ctx* c) { return c ? (c->salted ? (int)c->n_salts : 0) : A5X_E_ARG; }
+
+int a5x_salt_get(a5x_ctx* c, uint32_t index, uint8_t* out, size_t cap, size_t* out_len) {
+  if (!c || !out_len) return A5X_E_ARG;
+  if (!c->salted || index >= c->n_salts) return fail(c, A5X_E_ARG, "salt %u of %u", index, c->salted ? c->n_salts : 0u);
+  const size_t sl = (size_t)(c->s_off[index + 1] - c->s_off[index]);
+  *out_len = sl;
+  if (!out) return A5X_OK;
+  if (cap < sl) return fail(c, A5X_E_CAPACITY, "salt of %zu bytes, buffer has %zu", sl, cap);
+  if (sl) memcpy(out, c->s_bytes.data() + c->s_off[index], sl);
+  return A5X_OK;
+}
+
+int a5x_hit_salts(a5x_ctx* c, uint32_t* salt_out, uint64_t cap, uint64_t* n) {
+  if (!c || !n) return A5X_E_ARG;
+  *n = c->s_hit_salt.size();
+  if (!salt_out) return A5X_OK;
+  if (cap < c->s_hit_salt.size())
+    return fail(c, A5X_E_CAPACITY, "%zu hit salts, buffer has %llu", c->s_hit_salt.size(), (unsigned long long)cap);
+  if (!c->s_hit_salt.empty()) memcpy(salt_out, c->s_hit_salt.data(), c->s_hit_salt.size() * 4);
+  return A5X_OK;
+}
+
+int a5x_salts_last(a5x_ctx* c, uint64_t* hashed, uint64_t* skipped) {
+  if (!c) return A5X_E_ARG;
+  if (hashed) *hashed = c->s_hashed;
+  if (skipped) *skipped = c->s_skipped;
+  return A5X_OK;
+}
+
+int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_t* d_lines, uint64_t nbytes,
+                                   uint8_t* d_dig, uint64_t cap, uint64_t* n_lines, void* stream) {
+  if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
+  if (!c || (nbytes && !d_lines)) return A5X_E_ARG;
+  if (!algo_size(algo) || algo == A5X_ALGO_NTLM) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
+  if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) return fail(c, A5X_E_ARG, "bad salt order %d", order);
+  if (!c->salted || !c->n_salts) return fail(c, A5X_E_ARG, "no salted target set (a5x_set_salted_targets)");
+  if (((uintptr_t)d_lines & 15u) != 0) return fail(c, A5X_E_ARG, "d_lines must be 16-byte aligned");
+  if (((uintptr_t)d_dig & 3u) != 0) return fail(c, A5X_E_ARG, "d_digests must be 4-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (n_lines) *n_lines = 0;
+  c->s_hashed = c->s_skipped = 0;
+  c->s_hit_salt.clear();
+  if (!nbytes) return A5X_OK;
+  int rc;
+  const uint64_t nblk = a5x_salt_blocks(nbytes);
+  if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
+      (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)) || (rc = grow(c, c->r_counter, 2)))
+    return rc;
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 64, st));
+  HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, st));
+  A5xSaltLaunch SL;
+  SL.d = dig_launch(c);
+  SL.d.algo = algo;
+  SL.d.out = d_lines;
+  SL.d.nbytes = nbytes;
+  SL.d.blk_cnt = c->dg_blk_cnt.p;
+  SL.salts = c->s_table.p;
+  SL.nsalts = c->n_salts;
+  SL.order = order;
+  SL.hit_salt = nullptr;
+  SL.skipped = c->r_counter.p;
+  HIPCHK(c, a5x_launch_salt_stream(SL, 1, (uint32_t)std::max(1, c->cus), st));
+  HIPCHK(c, a5x_launch_scan(c->dg_blk_cnt.p, c->dg_blk_cnt.p, nblk, c->dg_blk_pre.p, c->dg_blk_pre.p, c->scan_tmp.p,
+                            c->d_scalars + 2, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_totals + 2, c->dg_blk_pre.p + nblk, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const uint64_t lines = c->h_totals[2];
+  if (n_lines) *n_lines = lines;
+  if (lines > cap / c->n_salts || !d_dig)
+    return fail(c, A5X_E_CAPACITY, "%llu lines x %u salts, digest buffer has room for %llu", (unsigned long long)lines,
+                c->n_salts, (unsigned long long)cap);
+  SL.d.blk_cnt = nullptr;
+  SL.d.blk_pre = c->dg_blk_pre.p;
+  SL.d.dig_out = d_dig;
+  HIPCHK(c, a5x_launch_salt_stream(SL, 2, (uint32_t)std::max(1, c->cus), st));
+  unsigned long long skp = 0;
+  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(&skp, c->r_counter.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (skp > lines * c->n_salts) return fail(c, A5X_E_HIP, "more skipped pairs than pairs");
+  c->s_skipped = skp;
+  c->s_hashed = lines * c->n_salts - skp;
+  return decode_dev_err(c, c->h_scalars[2]);
+}
+
+// RFC 1321 compression on the host (the device core, a5x_md.h, is device code): the message
+// words come from the same padded-source loop the kernels' md5_src runs
+extern "C++" {
+static void md5_block_host(uint32_t* st, const uint32_t* M) {
+  static const uint32_t K[64] = {
+      0xd76aa478u, 0xe8c7b756u, 0x242070dbu, 0xc1bdceeeu, 0xf57c0fafu, 0x4787c62au, 0xa8304613u, 0xfd469501u,
+      0x698098d8u, 0x8b44f7afu, 0xffff5bb1u, 0x895cd7beu, 0x6b901122u, 0xfd987193u, 0xa679438eu, 0x49b40821u,
+      0xf61e2562u, 0xc040b340u, 0x265e5a51u, 0xe9b6c7aau, 0xd62f105du, 0x02441453u, 0xd8a1e681u, 0xe7d3fbc8u,
+      0x21e1cde6u, 0xc33707d6u, 0xf4d50d87u, 0x455a14edu, 0xa9e3e905u, 0xfcefa3f8u, 0x676f02d9u, 0x8d2a4c8au,
+      0xfffa3942u, 0x8771f681u, 0x6d9d6122u, 0xfde5380cu, 0xa4beea44u, 0x4bdecfa9u, 0xf6bb4b60u, 0xbebfbc70u,
+      0x289b7ec6u, 0xeaa127fau, 0xd4ef3085u, 0x04881d05u, 0xd9d4d039u, 0xe6db99e5u, 0x1fa27cf8u, 0xc4ac5665u,
+      0xf4292244u, 0x432aff97u, 0xab9423a7u, 0xfc93a039u, 0x655b59c3u, 0x8f0ccc92u, 0xffeff47du, 0x85845dd1u,
+      0x6fa87e4fu, 0xfe2ce6e0u, 0xa3014314u, 0x4e0811a1u, 0xf7537e82u, 0xbd3af235u, 0x2ad7d2bbu, 0xeb86d391u};
+  static const uint32_t R[16] = {7, 12, 17, 22, 5, 9, 14, 20, 4, 11, 16, 23, 6, 10, 15, 21};
+  uint32_t a = st[0], b = st[1], c = st[2], d = st[3];
+  for (uint32_t i = 0; i < 64; i++) {
+    uint32_t f, g;
+    if (i < 16) { f = (b & c) | (~b & d); g = i; }
+    else if (i < 32) { f = (d & b) | (~d & c); g = (5 * i + 1) & 15; }
+    else if (i < 48) { f = b ^ c ^ d; g = (3 * i + 5) & 15; }
+    else { f = c ^ (b | ~d); g = (7 * i) & 15; }
+    const uint32_t x = a + f + K[i] + M[g], s = R[(i >> 4) * 4 + (i & 3)];
+    a = d; d = c; c = b;
+    b += (x << s) | (x >> (32 - s));
+  }
+  st[0] += a; st[1] += b; st[2] += c; st[3] += d;
+}
+template <class S> static void md5_src_host(const S& src, uint32_t len, uint32_t* d) {
+  d[0] = 0x67452301u; d[1] = 0xefcdab89u; d[2] = 0x98badcfeu; d[3] = 0x10325476u;
+  const uint32_t nb = (len + 8u) / 64u + 1u;
+  for (uint32_t blk = 0; blk < nb; blk++) {
+    uint32_t M[16];
+    for (uint32_t j = 0; j < 16; j++) {
+      const uint32_t b = blk * 64u + 4u * j;
+      const int k = (int)len - (int)b;
+      const uint32_t raw = k > 0 ? src.at4(b) : 0u;
+      M[j] = (raw & rule_keep(k)) | ((k >= 0 && k < 4) ? (0x80u << (8 * k)) : 0u);
+    }
+    if (blk == nb - 1) {
+      M[14] = len << 3;
+      M[15] = len >> 29;
+    }
+    md5_block_host(d, M);
+  }
+}
+}  // extern "C++"
+
+int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t slen, const uint8_t* msg, size_t len,
+                            uint8_t* out, size_t cap) {
+  const uint32_t W = algo_size(algo);
+  if (!W || algo == A5X_ALGO_NTLM || (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) ||
+      (!salt && slen) || (!msg && len) || !out || slen > A5X_SALT_MAX)
+    return A5X_E_ARG;
+  if (cap < W) return A5X_E_CAPACITY;
+  if (len > A5X_RULE_LMAX || !salt_fits((uint32_t)len, (uint32_t)slen)) return A5X_E_UNSUPPORTED;  // a skipped pair
+  uint32_t rec[A5X_SALT_STRIDE] = {0}, w[A5X_RULE_NDW] = {0};
+  rec[A5X_SALT_R_LEN] = (uint32_t)slen;
+  if (slen) memcpy(rec + A5X_SALT_R_BYTES, salt, slen);
+  SaltRec sr;
+  sr.r = rec;
+  SaltBuf b;
+  b.w = w;
+  SaltCandBytes cand;
+  cand.p = msg;
+  cand.n = (uint32_t)len;
+  if (order == A5X_SALT_ORDER_PASS_SALT) {
+    const uint32_t dirty = salt_copy_cand(b, cand, (uint32_t)len, 0u);
+    salt_append(b, (uint32_t)len, dirty, sr, (uint32_t)slen);
+  } else {
+    salt_prefix_cand(b, cand, (uint32_t)len, (uint32_t)slen, 0u);
+    salt_prefix_salt(b, sr, (uint32_t)slen);
+  }
+  const uint32_t L = (uint32_t)(len + slen);
+  // (test hook: the zero-past-the-message invariant of a5x_salt.h holds after the placement)
+  for (uint32_t i = L; i < 4u * A5X_RULE_NDW; i++)
+    if (((const uint8_t*)w)[i]) return A5X_E_BOUNDS;
+  uint32_t d[16];
+  switch (algo) {
+    case A5X_ALGO_MD5: md5_src_host(b, L, d); break;
+    case A5X_ALGO_SHA1: sha_digest<A5X_ALGO_SHA1>(b, L, d); break;
+    case A5X_ALGO_SHA256: sha_digest<A5X_ALGO_SHA256>(b, L, d); break;
+    case A5X_ALGO_SHA224: sha_digest<A5X_ALGO_SHA224>(b, L, d); break;
+    case A5X_ALGO_SHA384: sha_digest<A5X_ALGO_SHA384>(b, L, d); break;
+    default: sha_digest<A5X_ALGO_SHA512>(b, L, d); break;
+  }
+  memcpy(out, d, W);
   return A5X_OK;
 }
 
@@ -2701,9 +3091,11 @@ int a5x_format_plain(const uint8_t* plain, size_t len, uint8_t* out, size_t cap,
 }
 
 // a5x_format_hits, and with hit_rule a5x_format_hits_rules: each regenerated plain goes
-// through its hit's rule on the host (the interpreter the kernel ran)
+// through its hit's rule on the host (the interpreter the kernel ran); with hit_salt
+// a5x_format_hits_salted: "hexdigest:salt:plain", the salt raw or (hex_salt) in hex
 static int format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw, int mode, int mn, int mx,
-                       const a5x_hit* hits, uint64_t n_hits, const uint32_t* hit_rule, a5x_sink_fn sink, void* user) {
+                       const a5x_hit* hits, uint64_t n_hits, const uint32_t* hit_rule, a5x_sink_fn sink, void* user,
+                       const uint32_t* hit_salt = nullptr, int hex_salt = 0) {
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || !sink || (n_hits && (!hits || !words || !woff))) return A5X_E_ARG;
   if (!n_hits) return A5X_OK;
@@ -2826,6 +3218,15 @@ static int format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, u
       o += hx[full[(size_t)dsz * h + i] & 15];
     }
     o += ':';
+    if (hit_salt) {
+      if (!c->salted || hit_salt[h] >= c->n_salts)
+        return fail(c, A5X_E_ARG, "hit salt %u of %u in the set", hit_salt[h], c->salted ? c->n_salts : 0u);
+      for (uint64_t i = c->s_off[hit_salt[h]]; i < c->s_off[hit_salt[h] + 1]; i++) {
+        if (hex_salt) { o += hx[c->s_bytes[i] >> 4]; o += hx[c->s_bytes[i] & 15]; }
+        else o += (char)c->s_bytes[i];
+      }
+      o += ':';
+    }
     if (hit_rule) {
       if (hit_rule[h] >= c->n_rules) return fail(c, A5X_E_ARG, "hit rule %u of %u loaded", hit_rule[h], c->n_rules);
       if (plain[k].size() > A5X_RULE_LMAX) return fail(c, A5X_E_ARG, "hit candidate longer than the rule limit");
@@ -2859,6 +3260,13 @@ int a5x_format_hits_rules(a5x_ctx* c, const uint8_t* words, const uint64_t* woff
   return format_hits(c, words, woff, nw, mode, mn, mx, hits, n_hits, hit_rule, sink, user);
 }
 
+int a5x_format_hits_salted(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw, int mode, int mn,
+                           int mx, const a5x_hit* hits, uint64_t n_hits, const uint32_t* hit_salt, int hex_salt,
+                           a5x_sink_fn sink, void* user) {
+  if (c && n_hits && !hit_salt) return fail(c, A5X_E_ARG, "no salt indices");
+  return format_hits(c, words, woff, nw, mode, mn, mx, hits, n_hits, nullptr, sink, user, hit_salt, hex_salt);
+}
+
 // ---- rules (a5x_rules.h, a5x_rules.hip) -----------------------------------------
 int a5x_set_rules(a5x_ctx* c, const uint8_t* text, size_t len, uint32_t* n_rules, uint32_t* n_skipped) {
   if (!c || (len && !text)) return A5X_E_ARG;
@@ -2878,6 +3286,9 @@ int a5x_set_rules(a5x_ctx* c, const uint8_t* text, size_t len, uint32_t* n_rules
     }
     p = e + 1;
   }
+  if (nr && c->salted)
+    return fail(c, A5X_E_UNSUPPORTED, "rules and salted targets together are not supported: the target set is salted (%u salts)",
+                c->n_salts);
   if (c->device >= 0 && nr) {
     int rc;
     HIPCHK(c, hipSetDevice(c->device));

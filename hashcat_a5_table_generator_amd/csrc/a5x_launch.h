@@ -296,3 +296,19 @@ uint64_t a5x_rules_blocks(uint64_t nbytes);
 // digest to d.dig_out at index line * nrules + rule (a rejected line's are zero)
 // (cus: the device's compute units; the grid is cus x the workgroups a CU holds at once)
 hipError_t a5x_launch_rules_stream(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st);
+
+// ---- salted target lists in the digest + lookup stage (a5x_salt.hip) -----------
+struct A5xSaltLaunch {
+  A5xDigLaunch d;               // the stream, target set (keyed on the masked digests) and hit buffer (blocks of 4 KiB)
+  const uint32_t* salts;        // nsalts records of A5X_SALT_STRIDE u32 (a5x_salt.h), sorted by salt length
+  uint32_t nsalts;
+  int order;                    // A5X_SALT_ORDER_PASS_SALT / A5X_SALT_ORDER_SALT_PASS
+  uint32_t* hit_salt;           // op 0: the public salt index of hit h, beside d.hits
+  unsigned long long* skipped;  // += (line, salt) pairs whose message would exceed A5X_RULE_LMAX (not hashed)
+};
+size_t a5x_salt_lds();
+uint64_t a5x_salt_blocks(uint64_t nbytes);
+// op 0: hash + probe every (line, salt); op 1: line starts per block (d.blk_cnt); op 2: every
+// digest to d.dig_out at index line * nsalts + public salt index (a skipped pair's is zero)
+// (cus: the device's compute units; the grid is cus x the workgroups a CU holds at once)
+hipError_t a5x_launch_salt_stream(const A5xSaltLaunch& L, int op, uint32_t cus, hipStream_t st);

@@ -42,6 +42,8 @@ ALGO_SHA256 = 3  # FIPS 180-4 over the candidate bytes (hashcat -m 1400)
 ALGO_SHA224 = 5  # FIPS 180-4 over the candidate bytes (hashcat -m 1300)
 ALGO_SHA384 = 6  # FIPS 180-4 over the candidate bytes (hashcat -m 10800)
 ALGO_SHA512 = 7  # FIPS 180-4 over the candidate bytes (hashcat -m 1700)
+ORDER_PASS_SALT = 0  # salted sets: hash(candidate + salt), hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710
+ORDER_SALT_PASS = 1  # hash(salt + candidate), hashcat -m 20 / 120 / 1320 / 1420 / 10820 / 1720
 
 SubMap = Dict[bytes, List[bytes]]
 
@@ -342,6 +344,96 @@ class Context:
                                                         ctypes.byref(n), stream or None))
         return n.value
 
+    # ---- salted target lists (a5x_salt.hip) ----------------------------------------
+    def set_salted_targets(self, algo: int, order: int, digests, salts: Sequence[bytes]) -> None:
+        """Salted target set: digest i (``digest_size(algo)`` bytes each, bytes or an (n, size)
+        uint8 array) registered with ``salts[i]`` (at most 64 bytes).  order ``ORDER_PASS_SALT``:
+        hash(candidate + salt); ``ORDER_SALT_PASS``: hash(salt + candidate).  While the set is
+        salted every expand_digest* call hashes each candidate once per distinct salt;
+        ``last_hit_salts()`` names each hit's salt."""
+        buf = np.ascontiguousarray(np.frombuffer(bytes(digests), dtype=np.uint8) if isinstance(digests, (bytes, bytearray))
+                                   else np.asarray(digests, dtype=np.uint8)).reshape(-1)
+        size = self._L.a5x_digest_size(algo)
+        if size <= 0:  # (a5x_set_salted_targets names the bad algorithm)
+            size = 16
+        salts = [bytes(s) for s in salts]
+        if buf.size % size or buf.size // size != len(salts):
+            raise ValueError(f"digests must be {size} bytes each, one salt per digest")
+        sb = np.frombuffer(b"".join(salts) + b"\0", dtype=np.uint8)
+        so = np.zeros(len(salts) + 1, dtype=np.uint64)
+        if salts:
+            so[1:] = np.cumsum([len(s) for s in salts])
+        self._chk(self._L.a5x_set_salted_targets(self.h, algo, order, buf.ctypes.data if buf.size else None, len(salts),
+                                                 sb.ctypes.data, so.ctypes.data))
+        self._algo_size = size
+
+    def load_salted_hashes(self, algo: int, order: int, text: bytes, hex_salt: bool = False) -> Tuple[int, int, int]:
+        """Salted target set from the text of a ``hexdigest:salt`` file; returns (targets, distinct
+        salts, lines skipped)."""
+        text = text.encode() if isinstance(text, str) else bytes(text)
+        nt, ns, sk = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._L.a5x_load_salted_hashes(self.h, algo, order, text, len(text), 1 if hex_salt else 0,
+                                                 ctypes.byref(nt), ctypes.byref(ns), ctypes.byref(sk)))
+        self._algo_size = max(16, self._L.a5x_digest_size(algo))
+        return nt.value, ns.value, sk.value
+
+    def salt_count(self) -> int:
+        """Distinct salts of the current target set (0: not salted)."""
+        return self._L.a5x_salt_count(self.h)
+
+    def salt(self, index: int) -> bytes:
+        out = (ctypes.c_uint8 * 64)()
+        n = ctypes.c_size_t()
+        self._chk(self._L.a5x_salt_get(self.h, index, out, 64, ctypes.byref(n)))
+        return bytes(out[: n.value])
+
+    def last_hit_salts(self) -> List[int]:
+        """Salt index of each hit the latest expand_digest* call returned, in hit order."""
+        n = ctypes.c_uint64()
+        self._chk(self._L.a5x_hit_salts(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(1, n.value), dtype=np.uint32)
+        self._chk(self._L.a5x_hit_salts(self.h, out.ctypes.data, out.size, ctypes.byref(n)))
+        return [int(x) for x in out[: n.value]]
+
+    def salts_last(self) -> Tuple[int, int]:
+        """((candidate, salt) pairs hashed, pairs skipped as longer than 128 bytes) of the latest salted call."""
+        h, s = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._L.a5x_salts_last(self.h, ctypes.byref(h), ctypes.byref(s)))
+        return h.value, s.value
+
+    def digest_lines_salted_device(self, algo: int, order: int, d_lines: int, nbytes: int, d_digests: int, cap: int,
+                                   stream: int = 0) -> int:
+        """Digest of every (line, salt) of a device "cand\\n" stream under the salts of the current
+        set, at index line * S + salt (cap counts digests; a pair over 128 bytes gives a zero
+        digest); returns the line count."""
+        n = ctypes.c_uint64()
+        self._chk(self._L.a5x_digest_lines_salted_device(self.h, algo, order, d_lines, nbytes, d_digests or None, cap,
+                                                         ctypes.byref(n), stream or None))
+        return n.value
+
+    def format_hits_salted(self, words: np.ndarray, offs: np.ndarray, hits, salts, mode: int = MODE_DEFAULT,
+                           mn: int = 0, mx: int = 15, hex_salt: bool = False) -> bytes:
+        """hashcat "hexdigest:salt:plain\\n" lines for hits of this batch against a salted set
+        (a5x_format_hits_salted); salts: each hit's salt index (``last_hit_salts()``)."""
+        arr = (_lib.Hit * max(1, len(hits)))()
+        for k, (w, c, d) in enumerate(hits):
+            arr[k].word, arr[k].cand = int(w), int(c)
+            ctypes.memmove(arr[k].digest, bytes(d)[:16], 16)
+        sa = np.ascontiguousarray(salts, dtype=np.uint32)
+        if sa.size != len(hits):
+            raise ValueError("one salt index per hit")
+        chunks: List[bytes] = []
+
+        def _cb(_u, p, n):
+            chunks.append(ctypes.string_at(p, n))
+            return 0
+
+        cb = _lib.SINK(_cb)
+        self._chk(self._L.a5x_format_hits_salted(self.h, words.ctypes.data, offs.ctypes.data, len(offs) - 1, mode, mn,
+                                                 mx, arr, len(hits), sa.ctypes.data if sa.size else None,
+                                                 1 if hex_salt else 0, cb, None))
+        return b"".join(chunks)
+
     def format_hits(self, words: np.ndarray, offs: np.ndarray, hits, mode: int = MODE_DEFAULT, mn: int = 0,
                     mx: int = 15, rules=None) -> bytes:
         """hashcat "hexdigest:plain\\n" lines for hits [(word, cand, digest)] of this batch
@@ -447,6 +539,16 @@ def apply_rule(rule: bytes, word: bytes) -> bytes:
         raise ValueError(f"unsupported or malformed rule {rule!r} (or a word over 128 bytes)")
     check(rc)
     return bytes(out[: n.value])
+
+
+def debug_digest_salted(algo: int, order: int, salt: bytes, msg: bytes) -> bytes:
+    """hash(msg + salt) (order 0) or hash(salt + msg) (order 1) on the host by the message
+    assembly and digest cores the salt kernel runs (``a5x_debug_digest_salted``); A5xError
+    (A5X_E_UNSUPPORTED) for a pair the kernel skips: more than 128 message bytes."""
+    salt, msg = bytes(salt), bytes(msg)
+    out = (ctypes.c_uint8 * 64)()
+    check(_lib.load().a5x_debug_digest_salted(algo, order, salt, len(salt), msg, len(msg), out, 64))
+    return bytes(out[: digest_size(algo)])
 
 
 def partition(prefix: np.ndarray, parts: int) -> np.ndarray:

@@ -281,6 +281,58 @@ A5X_API int a5x_digest_lines_rules_device(a5x_ctx* ctx, int algo, const uint8_t*
 A5X_API int a5x_debug_apply_rule(const uint8_t* rule, size_t rule_len, const uint8_t* word, size_t len,
                                  uint8_t* out, size_t cap, size_t* out_len);
 
+/* ---- salted target lists: hash(pass.salt) and hash(salt.pass) (no reference counterpart:
+ * hashcat -m 10 / 20 (MD5), 110 / 120 (SHA-1), 1310 / 1320 (SHA-224), 1410 / 1420 (SHA-256),
+ * 10810 / 10820 (SHA-384), 1710 / 1720 (SHA-512)) ------------------------------------ */
+/* Replace the target set with a salted one: n digests of algo as in a5x_set_targets, target i
+ * registered with the salt salt_bytes[salt_off[i] .. salt_off[i+1]) (n + 1 offsets; at most 64
+ * bytes, 0 allowed: the unsalted digest).  order 0: the message is candidate + salt
+ * (pass.salt), order 1: salt + candidate (salt.pass).  Salts are deduplicated; a salt's index
+ * is its first appearance in the caller's order.  While the set is salted every
+ * a5x_expand_digest* call hashes each candidate once per distinct salt, and a digest computed
+ * under one salt matches only targets registered with that salt.  A (candidate, salt) pair
+ * whose message would exceed 128 bytes is skipped (not hashed) and counted.  A5X_E_ARG: NTLM
+ * (no salted mode) or an invalid algo, an order other than 0 / 1, a salt over 64 bytes;
+ * A5X_E_UNSUPPORTED: the context holds rules (rules and salts together are not supported;
+ * a5x_set_rules on a salted set answers the same).  On a host-only context the arguments are
+ * checked and the salts kept (a5x_salt_count / a5x_salt_get), nothing is uploaded.
+ * a5x_set_targets makes the set unsalted again. */
+A5X_API int a5x_set_salted_targets(a5x_ctx* ctx, int algo, int order, const uint8_t* digests, uint64_t n,
+                                   const uint8_t* salt_bytes, const uint64_t* salt_off);
+/* The same from the text of a "hexdigest:salt" file, one target per line ('\n', one trailing
+ * '\r' dropped, empty lines ignored): the salt is everything after the first ':' taken
+ * literally (it may contain ':'), or with hex_salt its hex decoding.  Lines with a bad digest,
+ * a bad hex salt, a salt over 64 bytes or no ':' are skipped and counted in *n_skipped. */
+A5X_API int a5x_load_salted_hashes(a5x_ctx* ctx, int algo, int order, const uint8_t* text, size_t len, int hex_salt,
+                                   uint64_t* n_targets, uint64_t* n_salts, uint64_t* n_skipped);
+/* Distinct salts of the context's salted set (0: the set is not salted), and salt `index`
+ * (*out_len = its size; out == NULL: size only; A5X_E_CAPACITY when cap is too small). */
+A5X_API int a5x_salt_count(const a5x_ctx* ctx);
+A5X_API int a5x_salt_get(a5x_ctx* ctx, uint32_t index, uint8_t* out, size_t cap, size_t* out_len);
+/* Latest a5x_expand_digest* call on a salted set: the salt index of each hit copied to the
+ * caller, in hit order (salt_out == NULL: *n only); a5x_salts_last: (candidate, salt) pairs
+ * hashed, and pairs skipped as longer than 128 bytes.  a5x_digest_lines_salted_device sets
+ * the two counts too. */
+A5X_API int a5x_hit_salts(a5x_ctx* ctx, uint32_t* salt_out, uint64_t cap, uint64_t* n);
+A5X_API int a5x_salts_last(a5x_ctx* ctx, uint64_t* hashed, uint64_t* skipped);
+/* a5x_format_hits for a salted set, "hexdigest:salt:plain\n" (hashcat's potfile form): the
+ * salt hit_salt[i] (n_hits entries, of the context's current set) raw, or in lowercase hex
+ * with hex_salt; the plain as a5x_format_plain writes it. */
+A5X_API int a5x_format_hits_salted(a5x_ctx* ctx, const uint8_t* words, const uint64_t* word_off, uint64_t n_words,
+                                   int mode, int min, int max, const a5x_hit* hits, uint64_t n_hits,
+                                   const uint32_t* hit_salt, int hex_salt, a5x_sink_fn sink, void* user);
+/* a5x_digest_lines_device under the S salts of the context's salted set, with algo and order
+ * given here: the digest of (line i, salt s) at index i * S + s; a skipped pair's digest is
+ * all zero.  digests_cap counts digests (lines x S); d_digests 4-B aligned.  Verification hook. */
+A5X_API int a5x_digest_lines_salted_device(a5x_ctx* ctx, int algo, int order, const uint8_t* d_lines, uint64_t nbytes,
+                                           uint8_t* d_digests, uint64_t digests_cap, uint64_t* n_lines, void* stream);
+/* Pure host: the digest of msg + salt (order 0) or salt + msg (order 1), the message placed
+ * by the a5x_salt.h code the kernel runs and hashed by the a5x_sha.h cores (MD5: an RFC 1321
+ * host compression over the same padded message words).  A5X_E_UNSUPPORTED for a pair the
+ * kernel would skip (len + slen > 128). */
+A5X_API int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t slen, const uint8_t* msg,
+                                    size_t len, uint8_t* out, size_t cap);
+
 /* Output byte offset, in the batch's full "cand\n" stream, of each global candidate index
  * cands[i] (cands[i] = the batch's total candidates gives its total bytes; larger: clamped).
  * Device-resident words; the keyspace runs once per call.  Candidate numbering is the one
