@@ -165,7 +165,7 @@ struct a5x_ctx {
   DevBuf<uint32_t> m_cl, m_cl2;  // mode-engine word lists (FAST probe -> k_mode_count_thread -> k_mode_count)
   uint8_t* gscr = nullptr;  // pass G scratch: A5X_G_SLOTS x a5x_gslot_bytes(), allocated on first use
   DevBuf<uint64_t> rec;  // FAST plan records (keyspace tiles of FW_TILE_REC u64)
-  uint32_t* d_scalars = nullptr;  // [0] defer_n, [1] nbig, [2] err, [3] nslow, [4] cplx_n, [5] slow segs, [6] BIG segs, [16..31] guard record
+  uint32_t* d_scalars = nullptr;  // [0] defer_n, [1] nbig, [2] err, [3] nslow, [4] cplx_n, [5] slow segs, [6] BIG segs, [16..31] guard record, [32] keyspace words walked twice (a5x_debug_keyspace_refit)
   uint32_t* h_scalars = nullptr;  // pinned
   uint64_t* h_totals = nullptr;   // pinned [0] cands [1] bytes [2..3] locate
 
@@ -530,7 +530,7 @@ int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uin
     d_byte_off = c->byte_off.p;
   }
   if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 128, st));  // scalars + guard debug record
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 132, st));  // scalars + guard debug record + [32]
   A5xKsLaunch K;
   memset(&K, 0, sizeof K);
   if (nw > 0) {
@@ -538,6 +538,7 @@ int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uin
     K.mn = mn; K.mx = mx; K.count = c->count.p; K.bytes = c->bytes.p; K.flags = c->flags.p;
     K.defer_list = c->defer.p; K.defer_n = c->d_scalars; K.nbig = c->d_scalars + 1; K.err = c->d_scalars + 2;
     K.hiflag = table_lead_only(c) ? c->d_scalars + 8 : nullptr;
+    K.nrefit = c->d_scalars + 32;
     K.nslow = c->d_scalars + 3;
     K.slow_list = c->slow_list.p; K.big_list = c->big_list.p;
     K.rec = c->rec.p; K.roff = c->roff.p;
@@ -818,7 +819,7 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
     d_byte_off = c->byte_off.p;
   }
   if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 128, st));
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 132, st));
   B->cand_off = d_cand_off;
   B->byte_off = d_byte_off;
   B->nbig = B->nslow = 0;
@@ -881,6 +882,7 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
     K.defer_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + 255) / 256, (uint64_t)c->cus * 2));
     K.vocc = vsub ? c->vocc.p : nullptr;
     K.hiflag = table_lead_only(c) ? c->d_scalars + 8 : nullptr;
+    K.nrefit = c->d_scalars + 32;
     HIPCHK(c, a5x_launch_keyspace(K, st));
     if (vsub) {
       K.vout_list = c->m_vl.p; K.vout_n = c->d_scalars + 15;
@@ -2375,6 +2377,17 @@ int a5x_expand_range(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uin
 int a5x_debug_stamps(unsigned long long* out16, int reset) {
   const int rc = a5x_read_stamps(out16, reset);
   return rc == 0 ? A5X_OK : (rc == -9 ? A5X_E_UNSUPPORTED : A5X_E_HIP);
+}
+
+int a5x_debug_keyspace_refit(a5x_ctx* c, uint64_t* out) {
+  if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
+  if (!c || !out) return A5X_E_ARG;
+  uint32_t n = 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(&n, c->d_scalars + 32, 4, hipMemcpyDeviceToHost));
+  *out = n;
+  return A5X_OK;
 }
 
 int a5x_debug_plan_word(a5x_ctx* c, const uint8_t* word, size_t len, int mn, int mx, uint8_t* out, size_t cap,

@@ -224,6 +224,7 @@ struct KsArgs {
   u32* vlong_list;  // k_keyspace_vsub small instantiation: the words for the large one
   u32* vlong_n;
   const u32* hiflag;  // k_keyspace_thread: the batch has bytes >= 0x80 (null: the byte walk only)
+  u32* nrefit;        // k_keyspace_thread: words whose lone matches the unit log did not hold (null: not counted)
 };
 
 // Whether the batch's words hold bytes >= 0x80, judged on its first 256 KiB (the choice
@@ -288,7 +289,8 @@ __device__ __forceinline__ u32 wave_append(bool pred, u32* ctr) {
 
 #ifndef KS_ABL
 #define KS_ABL 0  // keyspace timing ablations (variant builds only, wrong output): 1 no build pass,
-                  // 2 no planner in the count pass, 4 no record stores
+                  // 4 no record stores (2, no planner in the count pass, is gone: the build pass
+                  // checks its plan against the count pass's, so it never gave a figure)
 #endif
 
 // k_keyspace_thread's open group holds KS_GCAP entries (a unit with more choices
@@ -437,7 +439,7 @@ __device__ __forceinline__ void psk_walk(const LWord& lw, u32 L, bool act0, u32 
         cplx = true;
       } else {
         if (COUNT) count_unit(A, U);
-        if (!(KS_ABL & 2)) pl.unit(U);
+        pl.unit(U);
         cur_end = U.e;
         logit = true;
       }
@@ -466,11 +468,142 @@ __device__ __forceinline__ void psk_walk(const LWord& lw, u32 L, bool act0, u32 
   }
 }
 
+// The count pass of k_keyspace_thread in two loops.  psk_walk runs its unit block (lone_unit,
+// mode_unit, count_unit, the planner: three quarters of the body) at every position where
+// any lane of the wave has a lone match, which on a dictionary is nearly every position,
+// with a third of the lanes taking part.  psk_detect is psk_walk's detection alone: the
+// same three LDS reads and key tests per position, the same "complex" decisions that need
+// no key record (two matches, a key longer than 4 bytes, a match inside the last one's
+// span, which ends at q + the key length of kmatch), and the lone matches logged as
+// q << 10 | key.  psk_units then runs the unit block once per *unit index*, every lane on
+// its own u-th unit: wave max(units) bodies with most lanes busy, not wave max(L).
+// nlog = KS_ULOG + 1: the log does not hold the word (psk_detect stops there and the
+// caller walks the word with psk_walk, as before).
+template <bool UTF>
+__device__ __forceinline__ void psk_detect(const LWord& lw, u32 L, bool act0, u32 Lmax, u32 bmax, const Tab& T,
+                                           bool& cplx, uint16_t* ulog, u32& nlog) {
+  u32 cur_end = 0;
+  auto pos = [&](u32 q) -> u32 {
+    const u32 w4 = lds_ld4(lw.base, lw.off + q);
+    const u32 c1 = UTF && ((w4 >> 8) & 0xC0u) == 0x80u ? 1u : 0u;
+    const u32 c2 = c1 && ((w4 >> 16) & 0xC0u) == 0x80u ? 1u : 0u;
+    const u32 c3 = c2 && (w4 >> 30) == 2u ? 1u : 0u;
+    const u32 bk = T.bucket2[w4 & 255u];
+    const u32 ks = bk & 0xFFFFu, ke = bk >> 16;
+    const u32 nk1 = T.hdr->nkeys ? T.hdr->nkeys - 1u : 0u;
+    u32 nm = 0, kk = 0, kkl = 0;
+    u64 kmv[PSK_KB];
+#pragma unroll
+    for (u32 i = 0; i < PSK_KB; i++) kmv[i] = T.kmatch[min(ks + i, nk1)];
+    auto test = [&](u32 k2, u64 km) {
+      const u32 kl = (u32)(km >> 32) & 0xFFFFu;
+      if (k2 < ke && q + kl <= L) {
+        if (kl > 4) {
+          cplx = true;
+        } else {
+          const u32 m = kl >= 4 ? 0xFFFFFFFFu : ((1u << (8 * kl)) - 1u);
+          if ((w4 & m) == (u32)km) { nm++; kk = k2; kkl = kl; }
+        }
+      }
+    };
+#pragma unroll
+    for (u32 i = 0; i < PSK_KB; i++) test(ks + i, kmv[i]);
+    for (u32 i = PSK_KB; i < bmax; i++) test(ks + i, T.kmatch[min(ks + i, nk1)]);
+    if (nm > 1 || (nm == 1 && q < cur_end)) {
+      cplx = true;
+    } else if (nm == 1 && !cplx) {
+      const bool fits = nlog < KS_ULOG && kk < 1024u && q < 64u;
+      if (fits) ulog[nlog * 256u] = (uint16_t)((q << 10) | kk);
+      nlog = fits ? nlog + 1u : (u32)KS_ULOG + 1u;
+      cur_end = q + kkl;
+    }
+    return 1u + c1 + c2 + c3;
+  };
+  if constexpr (!UTF) {
+    for (u32 q = 0; q < Lmax; q++)
+      if (act0 && q < L && !cplx && nlog <= KS_ULOG) (void)pos(q);
+  } else {
+    u32 q = 0;
+    for (u32 it = 0; it < Lmax; it++) {
+      const bool act = act0 && q < L && !cplx && nlog <= KS_ULOG;
+      if (!__builtin_amdgcn_ballot_w64(act)) break;
+      if (act) q += pos(q);
+    }
+  }
+}
+
+// The unit block of psk_walk over the n logged lone matches of the lane's word, in their
+// order: the same lone_unit, repeat test, mode_unit, KS_GCAP check, count_unit and
+// pl.unit calls as the fused walk makes.  A unit that makes the word complex ends it.
+template <class PL>
+__device__ __forceinline__ void psk_units(const Tab& T, const uint16_t* ulog, u32 n, PL& pl, CountAcc& A, bool& cplx,
+                                          int rmode, bool logrep, bool& rep) {
+  u64 seen = 0;
+  const u32 nmax = wave_max_u32(n);
+  for (u32 u = 0; u < nmax; u++) {
+    if (u < n && !cplx) {
+      const u32 e = ulog[u * 256u], kk = e & 1023u;
+      Unit U;
+      lone_unit(T, e >> 10, kk, U);
+      const bool again = logrep && rmode >= 2 && ((seen >> (kk & 63u)) & 1u) &&
+                         (T.keys[kk].pad0 & (rmode == 2 ? 1u : 2u)) && T.keys[kk].nvals >= 1;
+      if (again) {
+        rep = true;
+      } else if (rmode && !mode_unit(T, U, rmode, seen, true)) {
+        cplx = true;
+      } else if (U.R > KS_GCAP) {
+        cplx = true;
+      } else {
+        count_unit(A, U);
+        pl.unit(U);
+      }
+    }
+  }
+}
+
+
+// Stable counting sort of a tile's 256 words by key (<= KS_ULOG + 1), for k_keyspace_thread:
+// lane tid brings word tid's key and info, and gets the word it owns from there on.  Each
+// wave counts its keys in 8-bit fields (<= 64 per wave) with five DPP scans, which also give
+// every lane its rank among the wave's equal keys; the (key, wave) histogram is scanned by
+// every wave for itself.  Sorted slot i goes to lane i % 64 of wave (i / 64 + rot) % 4.
+// Two barriers; sinfo / sperm / shist are free again after the second.
+__device__ __forceinline__ u32 ks_sort_tile(u32 key, u32 info, u32* sinfo, uint8_t* sperm, u32* shist, u32 tid,
+                                            u32 lane, u32 wv, u32 rot) {
+  constexpr u32 NK = KS_ULOG + 2, ND = (NK + 3) / 4;
+  static_assert(NK * 4 <= 128, "two registers per lane hold the (key, wave) histogram");
+  sinfo[tid] = info;
+  const u32 kd = key >> 2, ksh = 8u * (key & 3u);
+  u32 mine = 0, cnt = 0;
+#pragma unroll
+  for (u32 d = 0; d < ND; d++) {
+    const u32 p = wave_incl_scan_u32(kd == d ? 1u << ksh : 0u);
+    mine = kd == d ? p : mine;
+    cnt = (lane >> 2) == d ? lane63(p) : cnt;
+  }
+  const u32 rank = ((mine >> ksh) & 255u) - 1u;  // among the wave's lanes of this key
+  if (lane < NK) shist[lane * 4u + wv] = (cnt >> (8u * (lane & 3u))) & 255u;
+  __syncthreads();
+  const u32 h0 = shist[lane], h1 = lane < NK * 4u - 64u ? shist[64u + lane] : 0u;
+  const u32 s0 = wave_incl_scan_u32(h0), s1 = wave_incl_scan_u32(h1) + lane63(s0);
+  const u32 hi = key * 4u + wv;
+  const u32 b0 = (u32)__shfl((int)(s0 - h0), (int)(hi & 63u)), b1 = (u32)__shfl((int)(s1 - h1), (int)(hi & 63u));
+  const u32 slot = (hi < 64u ? b0 : b1) + rank;
+  sperm[((((slot >> 6) + rot) & 3u) << 6) | (slot & 63u)] = (uint8_t)tid;
+  __syncthreads();
+  return sperm[tid];
+}
 
 // One lane per word, one 256-word tile per workgroup iteration: classification,
 // closed-form (count, bytes), and for FAST words the plan record, packed densely
 // in word order inside the tile's record region (workgroup scan of the sizes).
 // The tile's word bytes are staged in LDS with 16-B loads.
+// Lane tid detects the lone matches of word tid (psk_detect); then the tile is sorted by
+// unit count (ks_sort_tile) and the lane works on the word it owns: the unit loops of the
+// count pass (psk_units) and of the build pass (the replay) run to the wave's largest unit
+// count, which the sort makes 3 / 4 / 6 / 10 on a dictionary instead of 9-10 in every wave.
+// Everything per word (counts, flags, lists, records, the vocc row) goes through the owned
+// word's index; nothing else depends on which lane did the work.
 template <bool UTF>
 __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
   // (hiflag: the batch has bytes >= 0x80 -- k_hibytes; the other instantiation does nothing)
@@ -480,16 +613,23 @@ __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
   u64* gbuf = (u64*)(smem + tb);                       // 256 x KS_GCAP open-group entries
   u32* wsum = (u32*)(smem + tb + 256 * KS_GCAP * 8);   // per-wave sums of the scan
   uint8_t* wb = smem + tb + 256 * KS_GCAP * 8 + 64;    // KS_WB + 32 tile bytes
-  uint16_t* ulog = (uint16_t*)(wb + KS_WB + 32) + threadIdx.x;  // KS_ULOG x 256 unit log
+  uint16_t* ulog = (uint16_t*)(wb + KS_WB + 32);       // KS_ULOG x 256 unit log, a column per word
+  uint16_t* srs = ulog + KS_ULOG * 256;                // 256 record sizes, then their scan, by word
+  // the sort's scratch lies in gbuf, which only the build pass uses: per-word info, the
+  // permutation, the key histogram by (key, wave)
+  u32* sinfo = (u32*)gbuf;
+  uint8_t* sperm = (uint8_t*)(sinfo + 256);
+  u32* shist = (u32*)(sperm + 256);
   load_table(smem, a.table, a.table_bytes);
   __syncthreads();
   const Tab T = tab_view(smem);
   const u32 bmax = T.hdr->max_bucket;
   const u32 tid = threadIdx.x, lane = lane_id(), wv = tid / 64;
   const u64 ntiles = (a.nw + FW_TILE - 1) / FW_TILE;
+  // which wave takes which quarter of the sorted tile turns with the workgroup, so that the
+  // workgroups sharing a CU do not all put their longest wave on the same SIMD
+  const u32 ks_rot = (blockIdx.x + (blockIdx.x >> 3) + (blockIdx.x >> 8)) & 3u;
   for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const u64 w = tile * FW_TILE + tid;
-    const bool valid = w < a.nw;
     const u64 t0 = tile * FW_TILE, t1 = min(a.nw, t0 + FW_TILE);
     const u64 A0 = a.woff[t0] & ~15ull, A1 = a.woff[t1];
     const bool staged = A1 - A0 <= KS_WB;
@@ -509,26 +649,60 @@ __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
       }
     }
     __syncthreads();
-    u64 s = 0, L64 = 0;
-    if (valid) {
-      s = a.woff[w];
-      L64 = a.woff[w + 1] - s;
+    // ---- detection, in word order: lane tid looks at word tid of the tile ----
+    u32 info, key;
+    {
+      const bool valid = t0 + tid < a.nw;
+      const u64 w = t0 + tid;
+      u64 s = 0, L64 = 0;
+      if (valid) {
+        s = a.woff[w];
+        L64 = a.woff[w + 1] - s;
+      }
+      const bool longw0 = valid && L64 > A5X_LMAX_A && a.mx >= 1;
+      const bool trivial0 = valid && (a.mx < 1 || L64 == 0);
+      bool cplx0 = valid && !longw0 && !trivial0 && !staged;
+      const bool psk0 = valid && !longw0 && !trivial0 && staged;
+      const u32 L0 = psk0 ? (u32)L64 : 0u;
+      LWord lw0;
+      lw0.base = wb; lw0.off = psk0 ? (u32)(s - A0) : 0u;
+      u32 nlog0 = 0;
+      psk_detect<UTF>(lw0, L0, psk0, wave_max_u32(L0), bmax, T, cplx0, ulog + tid, nlog0);
+      // what the word's later owner needs: LDS offset (< KS_WB + 16), length (<= A5X_LMAX_A),
+      // logged units (<= KS_ULOG + 1), the five flags
+      static_assert(KS_WB + 16 <= (1 << 14) && A5X_LMAX_A < (1 << 7) && KS_ULOG + 1 < (1 << 5), "info fields");
+      info = lw0.off | (L0 << 14) | (nlog0 << 21) | ((u32)valid << 26) | ((u32)longw0 << 27) | ((u32)trivial0 << 28) |
+             ((u32)psk0 << 29) | ((u32)cplx0 << 30);
+      key = psk0 && !cplx0 ? nlog0 : 0u;  // units to process (KS_ULOG + 1: the fused walk)
     }
-    const bool longw = valid && L64 > A5X_LMAX_A && a.mx >= 1;   // the wave DP kernel
-    const bool trivial = valid && (a.mx < 1 || L64 == 0);       // processWord emits nothing
-    bool cplx = valid && !longw && !trivial && !staged;
-    const bool psk = valid && !longw && !trivial && staged;
-    const u32 L = psk ? (u32)L64 : 0u;
+    // ---- the tile's words sorted by unit count: from here to the end of the iteration lane
+    // tid owns word own (a stable counting sort, so the order is the same in every run) ----
+    const u32 own = ks_sort_tile(key, info, sinfo, sperm, shist, tid, lane, wv, ks_rot);
+    info = sinfo[own];
+    const u64 w = t0 + own;
+    const bool valid = (info >> 26) & 1u, longw = (info >> 27) & 1u, trivial = (info >> 28) & 1u;
+    const bool psk = (info >> 29) & 1u;
+    bool cplx = (info >> 30) & 1u;
+    const u32 L = (info >> 14) & 127u;
+    u32 nlog = (info >> 21) & 31u;
     LWord lw;
-    lw.base = wb; lw.off = psk ? (u32)(s - A0) : 0u;
+    lw.base = wb; lw.off = info & 0x3FFFu;
+    const uint16_t* ulog_c = ulog + own;  // the owned word's log column
     // ---- pass 1: units -> counts + piece plan (count mode) ----
     CountAcc A;
     count_init(A, L);
     CountPlanner<KS_GCAP> pl;
-    u32 nlog = 0;
     const bool rm = a.rmode != 0;
     bool rep = false;  // (-s / -s -r with vocc: a repeated pattern; the occurrences logged)
-    psk_walk<true, UTF>(lw, L, psk, wave_max_u32(L), bmax, T, pl, A, cplx, a.rmode, ulog, &nlog, a.vocc != nullptr, rep);
+    const bool refit = nlog > KS_ULOG;  // the log does not hold the word
+    psk_units(T, ulog_c, psk && !cplx && !refit ? nlog : 0u, pl, A, cplx, a.rmode, a.vocc != nullptr, rep);
+    if (const u64 rfm = __builtin_amdgcn_ballot_w64(refit)) {
+      // such words take the fused walk from the start, here and in the build pass
+      if (a.nrefit && lane == (u32)__builtin_ctzll(rfm)) atomicAdd(a.nrefit, (u32)__popcll(rfm));
+      nlog = refit ? 0u : nlog;
+      psk_walk<true, UTF>(lw, L, refit, wave_max_u32(refit ? L : 0u), bmax, T, pl, A, cplx, a.rmode, ulog + own, &nlog,
+                          a.vocc != nullptr, rep);
+    }
     WordClass C;
     C.flags = 0; C.count = 0; C.bytes = 0; C.ovf = false; C.clusters = false;
     u32 f = 0;
@@ -555,12 +729,18 @@ __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
     // ---- record sizes -> exclusive workgroup scan ----
     const bool fast = psk && !cplx && (f & A5X_WF_FAST) && C.count > 0;
     const u32 rs = fast ? ff_rsize(f) : 0u;
-    const u32 inc = wave_incl_scan_u32(rs);
-    if (lane == 63) wsum[wv] = inc;
+    // (records are packed in word order, whoever owns the word: the sizes go to LDS by word,
+    // are scanned in word order, and the owner reads its word's offset back)
+    srs[own] = (uint16_t)rs;
     __syncthreads();
-    u32 base = 0;
-    for (u32 k = 0; k < wv; k++) base += wsum[k];
-    const u32 ro = base + inc - rs;
+    {
+      const u32 r = srs[tid], inc = wave_incl_scan_u32(r);
+      if (lane == 63) wsum[wv] = inc;
+      srs[tid] = (uint16_t)(inc - r);  // < 64 FW_RMAX
+    }
+    __syncthreads();
+    u32 ro = srs[own];
+    for (u32 k = 0; k < own / 64; k++) ro += wsum[k];
     const bool build = fast && ro + rs <= FW_TILE_REC;
     // ---- pass 2: the records of the FAST words (same walk, build mode) ----
     {
@@ -575,7 +755,7 @@ __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
       const u32 nrep = build && replay ? nlog : 0u;
       for (u32 i = 0; i < wave_max_u32((KS_ABL & 1) ? 0u : nrep); i++) {
         if (i < nrep) {
-          const u32 e = ulog[i * 256u];
+          const u32 e = ulog_c[i * 256u];
           Unit U;
           lone_unit(T, e >> 10, e & 1023u, U);
           u64 seen = 0;
@@ -622,7 +802,7 @@ __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
         u32 r[8];
 #pragma unroll
         for (u32 k = 0; k < 8; k++) {
-          const u32 e0 = 2 * k < nlog ? ulog[(2 * k) * 256u] : 0u, e1 = 2 * k + 1 < nlog ? ulog[(2 * k + 1) * 256u] : 0u;
+          const u32 e0 = 2 * k < nlog ? ulog_c[(2 * k) * 256u] : 0u, e1 = 2 * k + 1 < nlog ? ulog_c[(2 * k + 1) * 256u] : 0u;
           r[k] = e0 | (e1 << 16);
         }
         r[7] = (r[7] & 0xFFFFu) | ((logged ? nlog : 0xFFFFu) << 16);
@@ -3297,7 +3477,7 @@ hipError_t a5x_launch_keyspace(const A5xKsLaunch& L, hipStream_t st) {
   a.cplx_list = L.cplx_list; a.cplx_n = L.cplx_n; a.cplx_cap = L.cplx_cap; a.cplx_base = L.cplx_base;
   a.glob_list = L.glob_list; a.glob_n = L.glob_n; a.gscr = L.gscr;
   a.rmode = L.rmode; a.rcmin = L.rcmin; a.rnseg = L.rnseg; a.rseg = L.rseg; a.vocc = L.vocc;
-  a.hiflag = L.hiflag;
+  a.hiflag = L.hiflag; a.nrefit = L.nrefit;
   const dim3 kg(blocks_for(L.nw, FW_TILE, 65536));
   if (L.hiflag) {  // the table's keys start on UTF-8 lead bytes only: the walk by the batch's bytes
     hipLaunchKernelGGL(k_hibytes, dim3(256), dim3(256), 0, st, L.words, L.woff, L.nw, L.hiflag);
@@ -3336,7 +3516,7 @@ hipError_t a5x_launch_keyspace_g(const A5xKsLaunch& L, hipStream_t st) {
 }
 
 size_t a5x_keyspace_thread_lds(u32 table_bytes) {
-  return ((table_bytes + 15u) & ~15u) + FW_TILE * KS_GCAP * 8 + 64 + KS_WB + 32 + FW_TILE * KS_ULOG * 2;
+  return ((table_bytes + 15u) & ~15u) + FW_TILE * KS_GCAP * 8 + 64 + KS_WB + 32 + FW_TILE * KS_ULOG * 2 + FW_TILE * 2;
 }
 
 size_t a5x_keyspace_rprobe_lds(u32 table_bytes) {

@@ -53,6 +53,7 @@ struct A5xKsLaunch {
   uint32_t* vlong_list;  // k_keyspace_vsub: words the small-slot pass hands to the large one (null: large only)
   uint32_t* vlong_n;
   uint32_t* hiflag;      // zeroed u32: k_keyspace_thread walks UTF-8 words by lead bytes (null: by bytes)
+  uint32_t* nrefit;      // zeroed u32: k_keyspace_thread counts the words it walked with the fused psk_walk (null: no count)
 };
 
 // the virtual word list of a batch with virtual words (k_vwords_fill)

@@ -480,6 +480,14 @@ class Context:
                                               stream or None))
         return tc.value, tb.value
 
+    def keyspace_refit(self) -> int:
+        """Words of the last keyspace pass that ``k_keyspace_thread`` walked with the fused
+        position-synchronous walk because its unit log did not hold them
+        (``a5x_debug_keyspace_refit``; a test hook)."""
+        n = ctypes.c_uint64()
+        self._chk(self._L.a5x_debug_keyspace_refit(self.h, ctypes.byref(n)))
+        return n.value
+
     def locate_device(self, d_words: int, d_offs: int, n_words: int, cands, mode: int = MODE_DEFAULT, mn: int = 0,
                       mx: int = 15, stream: int = 0) -> np.ndarray:
         """Output byte offsets of global candidate indices (``a5x_locate_device``)."""

@@ -379,6 +379,13 @@ A5X_API int a5x_debug_plan_word(a5x_ctx* ctx, const uint8_t* word, size_t len, i
  * not fit the unit cache, 3 not a FAST word (no record); out[33..39] = 0. */
 A5X_API int a5x_debug_plan_sizes(a5x_ctx* ctx, const uint8_t* word, size_t len, uint32_t* out);
 
+/* Test hook (GPU test suite): how many words of the context's last keyspace pass (any
+ * a5x_keyspace* / a5x_expand* call, every mode) k_keyspace_thread could not hold in its
+ * per-word unit log (more than 16 lone matches, a match at byte >= 64, a key index
+ * >= 1024) and walked with the fused position-synchronous walk, twice, instead of by unit
+ * index.  Synchronises the device.  Never called by a compute path. */
+A5X_API int a5x_debug_keyspace_refit(a5x_ctx* ctx, uint64_t* out);
+
 /* Test hook (CPU test suite): the digest of msg[0, len) computed on the host by the
  * __host__ __device__ core the digest kernels run (a5x_sha.h; SHA-1 and the SHA-2 family),
  * a5x_digest_size(algo) bytes into out.  Never called by a compute path. */
