@@ -165,7 +165,8 @@ struct a5x_ctx {
   DevBuf<uint32_t> m_cl, m_cl2;  // mode-engine word lists (FAST probe -> k_mode_count_thread -> k_mode_count)
   uint8_t* gscr = nullptr;  // pass G scratch: A5X_G_SLOTS x a5x_gslot_bytes(), allocated on first use
   DevBuf<uint64_t> rec;  // FAST plan records (keyspace tiles of FW_TILE_REC u64)
-  uint32_t* d_scalars = nullptr;  // [0] defer_n, [1] nbig, [2] err, [3] nslow, [4] cplx_n, [5] slow segs, [6] BIG segs, [16..31] guard record, [32] keyspace words walked twice (a5x_debug_keyspace_refit)
+  bool ks_large_only = false;  // a5x_debug_keyspace_large_stage: the small word stage is not offered
+  uint32_t* d_scalars = nullptr;  // [0] defer_n, [1] nbig, [2] err, [3] nslow, [4] cplx_n, [5] slow segs, [6] BIG segs, [16..31] guard record, [32] keyspace words walked twice (a5x_debug_keyspace_refit), [33] largest tile span of the batch (k_tile_span), [34] word stage the keyspace pass used (a5x_debug_keyspace_stage)
   uint32_t* h_scalars = nullptr;  // pinned
   uint64_t* h_totals = nullptr;   // pinned [0] cands [1] bytes [2..3] locate
 
@@ -530,7 +531,7 @@ int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uin
     d_byte_off = c->byte_off.p;
   }
   if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 132, st));  // scalars + guard debug record + [32]
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 140, st));  // scalars + guard debug record + [32..34]
   A5xKsLaunch K;
   memset(&K, 0, sizeof K);
   if (nw > 0) {
@@ -539,6 +540,8 @@ int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uin
     K.defer_list = c->defer.p; K.defer_n = c->d_scalars; K.nbig = c->d_scalars + 1; K.err = c->d_scalars + 2;
     K.hiflag = table_lead_only(c) ? c->d_scalars + 8 : nullptr;
     K.nrefit = c->d_scalars + 32;
+    K.small_stage = c->ks_large_only ? 0u : a5x_keyspace_small_stage(c->table_bytes);
+    K.tspan = c->d_scalars + 33; K.stage_used = c->d_scalars + 34;
     K.nslow = c->d_scalars + 3;
     K.slow_list = c->slow_list.p; K.big_list = c->big_list.p;
     K.rec = c->rec.p; K.roff = c->roff.p;
@@ -819,7 +822,7 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
     d_byte_off = c->byte_off.p;
   }
   if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 132, st));
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 140, st));  // (with [32..34])
   B->cand_off = d_cand_off;
   B->byte_off = d_byte_off;
   B->nbig = B->nslow = 0;
@@ -883,6 +886,8 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
     K.vocc = vsub ? c->vocc.p : nullptr;
     K.hiflag = table_lead_only(c) ? c->d_scalars + 8 : nullptr;
     K.nrefit = c->d_scalars + 32;
+    K.small_stage = c->ks_large_only ? 0u : a5x_keyspace_small_stage(c->table_bytes);
+    K.tspan = c->d_scalars + 33; K.stage_used = c->d_scalars + 34;
     HIPCHK(c, a5x_launch_keyspace(K, st));
     if (vsub) {
       K.vout_list = c->m_vl.p; K.vout_n = c->d_scalars + 15;
@@ -2387,6 +2392,32 @@ int a5x_debug_keyspace_refit(a5x_ctx* c, uint64_t* out) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(&n, c->d_scalars + 32, 4, hipMemcpyDeviceToHost));
   *out = n;
+  return A5X_OK;
+}
+
+int a5x_debug_keyspace_small_stage(a5x_ctx* c, uint32_t* out) {
+  if (!c || !out) return A5X_E_ARG;
+  if (c->table.keys.empty()) return fail(c, A5X_E_NOTABLE, "no substitution table loaded");
+  if (c->table_dirty || c->blob.empty()) {
+    int rc = compile_table(c);
+    if (rc) return rc;
+  }
+  *out = a5x_keyspace_small_stage(c->table_bytes);
+  return A5X_OK;
+}
+
+int a5x_debug_keyspace_stage(a5x_ctx* c, uint32_t* out) {
+  if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
+  if (!c || !out) return A5X_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->d_scalars + 34, 4, hipMemcpyDeviceToHost));
+  return A5X_OK;
+}
+
+int a5x_debug_keyspace_large_stage(a5x_ctx* c, int on) {
+  if (!c) return A5X_E_ARG;
+  c->ks_large_only = on != 0;
   return A5X_OK;
 }
 

@@ -225,6 +225,10 @@ struct KsArgs {
   u32* vlong_n;
   const u32* hiflag;  // k_keyspace_thread: the batch has bytes >= 0x80 (null: the byte walk only)
   u32* nrefit;        // k_keyspace_thread: words whose lone matches the unit log did not hold (null: not counted)
+  u32 wstage;         // k_keyspace_thread: the word stage of this launch in bytes (KS_WB or the small stage)
+  u32 wsmall;         // the small stage offered for this batch (0: none, the launch with KS_WB runs)
+  const u32* tspan;   // the batch's largest tile span (k_tile_span); read when wsmall != 0
+  u32* stage_used;    // the stage of the launch that did the work (null: not reported)
 };
 
 // Whether the batch's words hold bytes >= 0x80, judged on its first 256 KiB (the choice
@@ -325,6 +329,12 @@ struct LWord {
 
 #ifndef KS_WB
 #define KS_WB 8192  // tile word bytes staged in LDS (larger tiles read global memory)
+#endif
+#ifndef KS_LDS5
+// LDS bytes of a workgroup of which five fit a CU; sizes the small stage.  gfx950 hands LDS out
+// in granules of 1280 B, 128 of them per CU: 25 granules each, not 160 KiB / 5 (a workgroup of
+// 32,768 B takes 26 and four stay resident: measured, profiles/ks_five_wg_ab_c3.txt)
+#define KS_LDS5 32000
 #endif
 
 template <class W>
@@ -604,16 +614,22 @@ __device__ __forceinline__ u32 ks_sort_tile(u32 key, u32 info, u32* sinfo, uint8
 // count, which the sort makes 3 / 4 / 6 / 10 on a dictionary instead of 9-10 in every wave.
 // Everything per word (counts, flags, lists, records, the vocc row) goes through the owned
 // word's index; nothing else depends on which lane did the work.
+// The word stage is a.wstage bytes: KS_WB, or the batch's small stage (a5x_keyspace_small_stage)
+// with which a fifth workgroup fits a CU's LDS.  The host enqueues <false> once with each;
+// the launch whose stage is not the batch's returns at once (k_tile_span: the small stage
+// when every tile fits it, so no word of a batch is staged by one launch and not the other).
 template <bool UTF>
-__global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
+__device__ __forceinline__ void ks_thread_tiles(const KsArgs& a) {
   // (hiflag: the batch has bytes >= 0x80 -- k_hibytes; the other instantiation does nothing)
   if (a.hiflag && (*a.hiflag != 0u) != UTF) return;
+  if (!UTF && (a.wstage == a.wsmall) != (a.wsmall && *a.tspan <= a.wsmall)) return;
+  if (a.stage_used && blockIdx.x == 0 && threadIdx.x == 0) *a.stage_used = a.wstage;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const u32 tb = (a.table_bytes + 15u) & ~15u;
   u64* gbuf = (u64*)(smem + tb);                       // 256 x KS_GCAP open-group entries
   u32* wsum = (u32*)(smem + tb + 256 * KS_GCAP * 8);   // per-wave sums of the scan
-  uint8_t* wb = smem + tb + 256 * KS_GCAP * 8 + 64;    // KS_WB + 32 tile bytes
-  uint16_t* ulog = (uint16_t*)(wb + KS_WB + 32);       // KS_ULOG x 256 unit log, a column per word
+  uint8_t* wb = smem + tb + 256 * KS_GCAP * 8 + 64;    // a.wstage + 32 tile bytes
+  uint16_t* ulog = (uint16_t*)(wb + a.wstage + 32);    // KS_ULOG x 256 unit log, a column per word
   uint16_t* srs = ulog + KS_ULOG * 256;                // 256 record sizes, then their scan, by word
   // the sort's scratch lies in gbuf, which only the build pass uses: per-word info, the
   // permutation, the key histogram by (key, wave)
@@ -629,10 +645,13 @@ __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
   // which wave takes which quarter of the sorted tile turns with the workgroup, so that the
   // workgroups sharing a CU do not all put their longest wave on the same SIMD
   const u32 ks_rot = (blockIdx.x + (blockIdx.x >> 3) + (blockIdx.x >> 8)) & 3u;
-  for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+  // one tile per workgroup (a5x_launch_keyspace's grid is the tile count): written as a loop of
+  // one pass for the -r path's early end of the tile; a real tile loop keeps its invariants
+  // in registers across the whole body and does not fit 96 VGPRs
+  for (u64 tile = blockIdx.x, once = 0; once == 0 && tile < ntiles; once = 1) {
     const u64 t0 = tile * FW_TILE, t1 = min(a.nw, t0 + FW_TILE);
     const u64 A0 = a.woff[t0] & ~15ull, A1 = a.woff[t1];
-    const bool staged = A1 - A0 <= KS_WB;
+    const bool staged = A1 - A0 <= a.wstage;
     if (staged) {
       const uint4* src = (const uint4*)(a.words + A0);
       const u32 nq = (u32)((A1 - A0 + 15) / 16);
@@ -829,6 +848,30 @@ __global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
     }
     __syncthreads();  // wb / wsum are rewritten by the next tile
   }
+}
+
+template <bool UTF>
+__global__ void __launch_bounds__(256) k_keyspace_thread(KsArgs a) {
+  ks_thread_tiles<UTF>(a);
+}
+// The byte walk is asked to fit five waves per SIMD (<= 96 VGPRs; with the small stage five
+// workgroups per CU).  The UTF-8 walk spills under that limit and stays at four.
+template <>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) k_keyspace_thread<false>(KsArgs a) {
+  ks_thread_tiles<false>(a);
+}
+
+// The largest tile span of the batch, woff[t1] - (woff[t0] & ~15) as k_keyspace_thread stages
+// it, into *span (zeroed): one atomic per wave.
+__global__ void __launch_bounds__(256) k_tile_span(const u64* woff, u64 nw, u32* span) {
+  const u64 ntiles = (nw + FW_TILE - 1) / FW_TILE;
+  u32 m = 0;
+  for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < ntiles; t += (u64)gridDim.x * blockDim.x) {
+    const u64 t0 = t * FW_TILE, t1 = min(nw, t0 + FW_TILE);
+    m = max(m, (u32)min(woff[t1] - (woff[t0] & ~15ull), (u64)0xFFFFFFFFu));
+  }
+  m = wave_max_u32(m);
+  if (m && lane_id() == 0) atomicMax(span, m);
 }
 
 #define RP_SLOT 80  // k_keyspace_rprobe: per-lane LDS word slot (words <= A5X_LMAX_A bytes + over-read)
@@ -3478,14 +3521,27 @@ hipError_t a5x_launch_keyspace(const A5xKsLaunch& L, hipStream_t st) {
   a.glob_list = L.glob_list; a.glob_n = L.glob_n; a.gscr = L.gscr;
   a.rmode = L.rmode; a.rcmin = L.rcmin; a.rnseg = L.rnseg; a.rseg = L.rseg; a.vocc = L.vocc;
   a.hiflag = L.hiflag; a.nrefit = L.nrefit;
-  const dim3 kg(blocks_for(L.nw, FW_TILE, 65536));
+  a.wstage = KS_WB; a.wsmall = L.tspan ? L.small_stage : 0u; a.tspan = L.tspan; a.stage_used = L.stage_used;
+  // a workgroup per tile (the callers bound the batch by its u32 record offsets, FW_TILE_REC
+  // u64 per tile, far below the grid limit)
+  if ((L.nw + FW_TILE - 1) / FW_TILE > 0xFFFFFFu) return hipErrorInvalidValue;
+  const dim3 kg(blocks_for(L.nw, FW_TILE, 0xFFFFFFu));
+  if (a.wsmall)  // the batch's largest tile against the small stage, for the two <false> launches below
+    hipLaunchKernelGGL(k_tile_span, dim3(blocks_for((L.nw + FW_TILE - 1) / FW_TILE, 256, 256)), dim3(256), 0, st, L.woff,
+                       L.nw, L.tspan);
   if (L.hiflag) {  // the table's keys start on UTF-8 lead bytes only: the walk by the batch's bytes
     hipLaunchKernelGGL(k_hibytes, dim3(256), dim3(256), 0, st, L.words, L.woff, L.nw, L.hiflag);
     // (the full grid: a resident one striding over the tiles measured slower on C5 -s, 19.3 vs
     // 17.9 ms keyspace; on an ASCII batch every workgroup returns at once)
-    hipLaunchKernelGGL(k_keyspace_thread<true>, kg, dim3(FW_TILE), a5x_keyspace_thread_lds(L.table_bytes), st, a);
+    hipLaunchKernelGGL(k_keyspace_thread<true>, kg, dim3(FW_TILE), a5x_keyspace_thread_lds(L.table_bytes, KS_WB), st, a);
   }
-  hipLaunchKernelGGL(k_keyspace_thread<false>, kg, dim3(FW_TILE), a5x_keyspace_thread_lds(L.table_bytes), st, a);
+  // (one of the two does the work: the small stage when every tile of the batch fits it)
+  hipLaunchKernelGGL(k_keyspace_thread<false>, kg, dim3(FW_TILE), a5x_keyspace_thread_lds(L.table_bytes, KS_WB), st, a);
+  if (a.wsmall) {
+    a.wstage = a.wsmall;
+    hipLaunchKernelGGL(k_keyspace_thread<false>, kg, dim3(FW_TILE), a5x_keyspace_thread_lds(L.table_bytes, a.wsmall), st,
+                       a);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (L.rmode) {  // -r / -s / -s -r FAST probe: k_keyspace_thread + the words it listed
@@ -3515,8 +3571,16 @@ hipError_t a5x_launch_keyspace_g(const A5xKsLaunch& L, hipStream_t st) {
   return hipGetLastError();
 }
 
-size_t a5x_keyspace_thread_lds(u32 table_bytes) {
-  return ((table_bytes + 15u) & ~15u) + FW_TILE * KS_GCAP * 8 + 64 + KS_WB + 32 + FW_TILE * KS_ULOG * 2 + FW_TILE * 2;
+size_t a5x_keyspace_thread_lds(u32 table_bytes, u32 stage) {
+  return ((table_bytes + 15u) & ~15u) + FW_TILE * KS_GCAP * 8 + 64 + stage + 32 + FW_TILE * KS_ULOG * 2 + FW_TILE * 2;
+}
+
+// The word stage with which k_keyspace_thread's workgroup is <= KS_LDS5 B of LDS (five per CU),
+// offered when it still holds a dictionary tile (>= 2048 B); 0: the table leaves no room.
+u32 a5x_keyspace_small_stage(u32 table_bytes) {
+  const size_t fixed = a5x_keyspace_thread_lds(table_bytes, 0);
+  if (fixed + 2048 > KS_LDS5) return 0;
+  return (u32)(KS_LDS5 - fixed) & ~15u;
 }
 
 size_t a5x_keyspace_rprobe_lds(u32 table_bytes) {

@@ -53,6 +53,9 @@ struct A5xKsLaunch {
   uint32_t* vlong_list;  // k_keyspace_vsub: words the small-slot pass hands to the large one (null: large only)
   uint32_t* vlong_n;
   uint32_t* hiflag;      // zeroed u32: k_keyspace_thread walks UTF-8 words by lead bytes (null: by bytes)
+  uint32_t small_stage;  // k_keyspace_thread<false>'s small word stage (a5x_keyspace_small_stage; 0: the large one only)
+  uint32_t* tspan;       // zeroed u32: the batch's largest tile span, which picks the stage (null: the large one only)
+  uint32_t* stage_used;  // u32: the stage of the k_keyspace_thread launch that did the work (null: not reported)
   uint32_t* nrefit;      // zeroed u32: k_keyspace_thread counts the words it walked with the fused psk_walk (null: no count)
 };
 
@@ -141,7 +144,8 @@ hipError_t a5x_launch_keyspace_g(const A5xKsLaunch& L, hipStream_t st);
 int a5x_read_stamps(unsigned long long* out16, int reset);
 hipError_t a5x_launch_keyspace(const A5xKsLaunch& L, hipStream_t st);
 size_t a5x_keyspace_wave_lds(uint32_t table_bytes);
-size_t a5x_keyspace_thread_lds(uint32_t table_bytes);
+size_t a5x_keyspace_thread_lds(uint32_t table_bytes, uint32_t stage);
+uint32_t a5x_keyspace_small_stage(uint32_t table_bytes);  // 0: not offered for this table
 size_t a5x_keyspace_rprobe_lds(uint32_t table_bytes);
 uint64_t a5x_scan_tmp_elems(uint64_t n);
 hipError_t a5x_launch_scan(const uint64_t* ca, const uint64_t* cb, uint64_t n, uint64_t* outa, uint64_t* outb,

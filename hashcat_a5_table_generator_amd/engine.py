@@ -488,6 +488,25 @@ class Context:
         self._chk(self._L.a5x_debug_keyspace_refit(self.h, ctypes.byref(n)))
         return n.value
 
+    def keyspace_small_stage(self) -> int:
+        """The small word stage of ``k_keyspace_thread`` for the loaded table in bytes, 0 when
+        the table leaves no room for one (``a5x_debug_keyspace_small_stage``; a test hook)."""
+        n = ctypes.c_uint32()
+        self._chk(self._L.a5x_debug_keyspace_small_stage(self.h, ctypes.byref(n)))
+        return n.value
+
+    def keyspace_stage(self) -> int:
+        """The word stage in bytes that the last keyspace pass used
+        (``a5x_debug_keyspace_stage``; a test hook)."""
+        n = ctypes.c_uint32()
+        self._chk(self._L.a5x_debug_keyspace_stage(self.h, ctypes.byref(n)))
+        return n.value
+
+    def keyspace_large_stage(self, on: bool = True) -> None:
+        """Stop (or resume) offering the small word stage on this context
+        (``a5x_debug_keyspace_large_stage``; tests and A/B runs)."""
+        self._chk(self._L.a5x_debug_keyspace_large_stage(self.h, 1 if on else 0))
+
     def locate_device(self, d_words: int, d_offs: int, n_words: int, cands, mode: int = MODE_DEFAULT, mn: int = 0,
                       mx: int = 15, stream: int = 0) -> np.ndarray:
         """Output byte offsets of global candidate indices (``a5x_locate_device``)."""

@@ -386,6 +386,21 @@ A5X_API int a5x_debug_plan_sizes(a5x_ctx* ctx, const uint8_t* word, size_t len, 
  * index.  Synchronises the device.  Never called by a compute path. */
 A5X_API int a5x_debug_keyspace_refit(a5x_ctx* ctx, uint64_t* out);
 
+/* Test hooks: the word stage of k_keyspace_thread, the LDS bytes that hold a tile's words.
+ * The byte walk has two: the large one (8192 B, four workgroups per CU) and a small one sized
+ * to the loaded table so that the workgroup takes <= 32,000 B of LDS (25 allocation granules
+ * of 1280 B; five workgroups per CU), used by a batch when every one of its 256-word tiles
+ * fits it; the choice changes no result.
+ * _small_stage: the small stage for the loaded table in bytes, 0 when the table leaves less
+ * than 2048 B (not offered; works on a host-only context).  _stage: the stage of the
+ * context's last keyspace pass (the large one for a UTF-8 batch walked by lead bytes; 0
+ * before any pass or after an empty batch); synchronises the device.  _large_stage(on):
+ * on != 0 stops offering the small stage on this context (tests, A/B runs).  Never called by a
+ * compute path. */
+A5X_API int a5x_debug_keyspace_small_stage(a5x_ctx* ctx, uint32_t* out);
+A5X_API int a5x_debug_keyspace_stage(a5x_ctx* ctx, uint32_t* out);
+A5X_API int a5x_debug_keyspace_large_stage(a5x_ctx* ctx, int on);
+
 /* Test hook (CPU test suite): the digest of msg[0, len) computed on the host by the
  * __host__ __device__ core the digest kernels run (a5x_sha.h; SHA-1 and the SHA-2 family),
  * a5x_digest_size(algo) bytes into out.  Never called by a compute path. */
