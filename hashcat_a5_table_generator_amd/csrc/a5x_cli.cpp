@@ -6,7 +6,8 @@
 //
 //   a5x_generator <dict-file> -t <table> [-t <table> ...] [-m N] [-x N]
 //                 [--threads N] [-s] [-r] [--device N]
-//                 [--hashes <file> [--algo md5|ntlm|sha1|sha224|sha256|sha384|sha512] [--rules <file>]
+//                 [--hashes <file> [--algo md5|ntlm|sha1|sha224|sha256|sha384|sha512|md5-md5|md5-md5-md5|
+//                                          md5-md5up|md5-sha1|sha1-sha1|sha1-md5|sha256-md5] [--rules <file>]
 //                                  [--salted=pass.salt|salt.pass [--hex-salt]]]
 //                 [--skip N] [--limit N] [--keyspace]
 //
@@ -68,7 +69,11 @@ static void usage(FILE* f) {
           "                                    before hashing (hashcat -r; long form only: -r is --reverse-sub)\n"
           "      --algo=md5                    Digest of --hashes: md5 (hashcat -m 0), ntlm (-m 1000),\n"
           "                                    sha1 (-m 100), sha224 (-m 1300), sha256 (-m 1400),\n"
-          "                                    sha384 (-m 10800) or sha512 (-m 1700); a name or the -m number\n"
+          "                                    sha384 (-m 10800) or sha512 (-m 1700); a name or the -m number;\n"
+          "                                    nested, a digest of the hex text of another: md5-md5 (-m 2600),\n"
+          "                                    md5-md5-md5 (-m 3500), md5-md5up (-m 4300, upper-case hex),\n"
+          "                                    md5-sha1 (-m 4400), sha1-sha1 (-m 4500), sha1-md5 (-m 4700),\n"
+          "                                    sha256-md5 (-m 20800); outer-inner, not with --salted\n"
           "      --salted=ORDER                With --hashes: FILE holds hash:salt lines; ORDER is pass.salt\n"
           "                                    (hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710) or salt.pass\n"
           "                                    (-m 20 / 120 / 1320 / 1420 / 10820 / 1720); --algo also takes\n"
@@ -387,8 +392,16 @@ int main(int argc, char** argv) {
       else if (v == "1410" || v == "1420") { algo = A5X_ALGO_SHA256; mode_order = v == "1420"; }
       else if (v == "1710" || v == "1720") { algo = A5X_ALGO_SHA512; mode_order = v == "1720"; }
       else if (v == "10810" || v == "10820") { algo = A5X_ALGO_SHA384; mode_order = v == "10820"; }
+      else if (v == "md5-md5" || v == "2600") algo = A5X_ALGO_MD5_MD5;
+      else if (v == "md5-md5-md5" || v == "3500") algo = A5X_ALGO_MD5_MD5_MD5;
+      else if (v == "md5-md5up" || v == "4300") algo = A5X_ALGO_MD5_MD5UP;
+      else if (v == "md5-sha1" || v == "4400") algo = A5X_ALGO_MD5_SHA1;
+      else if (v == "sha1-sha1" || v == "4500") algo = A5X_ALGO_SHA1_SHA1;
+      else if (v == "sha1-md5" || v == "4700") algo = A5X_ALGO_SHA1_MD5;
+      else if (v == "sha256-md5" || v == "20800") algo = A5X_ALGO_SHA256_MD5;
       else {
-        fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1, sha224, sha256, sha384 or sha512\n");
+        fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1, sha224, sha256, sha384 or sha512, or nested:\n"
+                        "md5-md5, md5-md5-md5, md5-md5up, md5-sha1, sha1-sha1, sha1-md5 or sha256-md5\n");
         return 80;
       }
     } else if (s.rfind("--salted", 0) == 0) {
@@ -461,6 +474,10 @@ int main(int argc, char** argv) {
   }
   if (order >= 0 && algo == A5X_ALGO_NTLM) {
     fprintf(stderr, "a5_generator: error: --salted with --algo ntlm: NTLM has no salted mode\n");
+    return 80;
+  }
+  if (order >= 0 && algo >= A5X_ALGO_MD5_MD5 && algo <= A5X_ALGO_SHA256_MD5) {
+    fprintf(stderr, "a5_generator: error: --salted with a nested --algo: the nested digests have no salted mode here\n");
     return 80;
   }
   if (!hashes.empty() && (cursor || keyspace_only)) {

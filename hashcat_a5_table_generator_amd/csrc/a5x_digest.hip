@@ -28,6 +28,9 @@
 #include "a5x_launch.h"
 #include "a5x_md.h"
 #include "a5x_sha.h"
+#ifdef A5X_DIGEST_NEST
+#include "a5x_nest.h"
+#endif
 
 namespace {
 
@@ -46,8 +49,7 @@ typedef uint32_t u32;
 #endif
 template <int ALGO> struct DCfg {
   static constexpr u32 BLK = ALGO == A5X_ALGO_MD5 ? 4096u : (ALGO == A5X_ALGO_NTLM ? 2048u : A5X_SHA_DBLK);
-  static constexpr u32 DW = ALGO == A5X_ALGO_SHA1 ? 5u : ALGO == A5X_ALGO_SHA256 ? 8u : ALGO == A5X_ALGO_SHA224 ? 7u
-                          : ALGO == A5X_ALGO_SHA384 ? 12u : ALGO == A5X_ALGO_SHA512 ? 16u : 4u;
+  static constexpr u32 DW = a5x_algo_words(ALGO);
   static constexpr u32 HT = a5x_hit_tail_stride(ALGO);  // words of a hit's tail record
   static_assert(DW <= 4u || DW - 4u <= HT, "the hit's tail record holds the whole tail");
 };
@@ -239,6 +241,14 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
       u32 d[DW];
       if constexpr (ALGO == A5X_ALGO_MD5) {
         md_digest<true>(W.data, s, a.out, bs + s, a.nbytes, in_lds, len, d);
+#ifdef A5X_DIGEST_NEST
+      } else if constexpr (a5x_algo_nested(ALGO)) {
+        ShaLine src;
+        src.lbase = W.data; src.loff = s;
+        src.gbase = a.out; src.goff = bs + s; src.glim = a.nbytes;
+        src.lds = in_lds;
+        nest_digest<ALGO>(src, len, d);
+#endif
       } else if constexpr (DW > 4) {
         ShaLine src;
         src.lbase = W.data; src.loff = s;
@@ -291,6 +301,7 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
   if (err) atomicOr(a.err, err);
 }
 
+#ifndef A5X_DIGEST_NEST
 // hits: (block, ordinal) -> global candidate index -> (word, candidate in word)
 __global__ void __launch_bounds__(64) k_hits_resolve(A5xHitRaw* hits, u32 n, const u64* blk_pre, u64 cand_base,
                                                       const u64* cand_off, u64 nw) {
@@ -331,7 +342,35 @@ __global__ void __launch_bounds__(64) k_gather_words(const uint8_t* words, const
   }
 }
 
+#endif  // A5X_DIGEST_NEST
+
 }  // namespace
+
+// The nested instantiations live in a translation unit of their own, a5x_digest_nest.hip,
+// which includes this file with A5X_DIGEST_NEST defined, for the reason recorded above
+// a5x_launch_rules_stream (a5x_rules.hip): the kernels of this module keep their code.
+#ifdef A5X_DIGEST_NEST
+template <int ALGO>
+static hipError_t nest_launch(const A5xDigLaunch& L, int op, uint32_t g, hipStream_t st) {
+  static_assert(DCfg<ALGO>::BLK == 4096u, "the nested algorithms take the MD5 / SHA stream block and its LDS layout");
+  hipLaunchKernelGGL(k_digest_stream<ALGO>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+  return hipGetLastError();
+}
+// (arguments checked and the grid sized by a5x_launch_digest_stream)
+hipError_t a5x_launch_digest_stream_nest(const A5xDigLaunch& L, int op, uint32_t g, hipStream_t st) {
+  switch (L.algo) {
+    case A5X_ALGO_MD5_MD5: return nest_launch<A5X_ALGO_MD5_MD5>(L, op, g, st);
+    case A5X_ALGO_MD5_MD5_MD5: return nest_launch<A5X_ALGO_MD5_MD5_MD5>(L, op, g, st);
+    case A5X_ALGO_MD5_MD5UP: return nest_launch<A5X_ALGO_MD5_MD5UP>(L, op, g, st);
+    case A5X_ALGO_MD5_SHA1: return nest_launch<A5X_ALGO_MD5_SHA1>(L, op, g, st);
+    case A5X_ALGO_SHA1_SHA1: return nest_launch<A5X_ALGO_SHA1_SHA1>(L, op, g, st);
+    case A5X_ALGO_SHA1_MD5: return nest_launch<A5X_ALGO_SHA1_MD5>(L, op, g, st);
+    case A5X_ALGO_SHA256_MD5: return nest_launch<A5X_ALGO_SHA256_MD5>(L, op, g, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+#else
+hipError_t a5x_launch_digest_stream_nest(const A5xDigLaunch& L, int op, uint32_t g, hipStream_t st);
 
 hipError_t a5x_launch_nonfast_list(const uint32_t* flags, const uint64_t* cand_off, uint64_t nw, uint64_t cb,
                                    uint64_t ce, uint32_t* list, uint32_t* n, hipStream_t st) {
@@ -359,7 +398,8 @@ static u32 digest_blk(int algo) {
   return algo == A5X_ALGO_MD5 ? DCfg<A5X_ALGO_MD5>::BLK : algo == A5X_ALGO_NTLM ? DCfg<A5X_ALGO_NTLM>::BLK
        : algo == A5X_ALGO_SHA1 ? DCfg<A5X_ALGO_SHA1>::BLK : algo == A5X_ALGO_SHA256 ? DCfg<A5X_ALGO_SHA256>::BLK
        : algo == A5X_ALGO_SHA224 ? DCfg<A5X_ALGO_SHA224>::BLK : algo == A5X_ALGO_SHA384 ? DCfg<A5X_ALGO_SHA384>::BLK
-       : algo == A5X_ALGO_SHA512 ? DCfg<A5X_ALGO_SHA512>::BLK : 0u;
+       : algo == A5X_ALGO_SHA512 ? DCfg<A5X_ALGO_SHA512>::BLK
+       : a5x_algo_nested(algo) ? DCfg<A5X_ALGO_MD5_MD5>::BLK : 0u;  // (one block for every nested form: nest_launch)
 }
 size_t a5x_digest_lds(int algo) {
   const u32 blk = digest_blk(algo);
@@ -371,7 +411,7 @@ hipError_t a5x_launch_digest_stream(const A5xDigLaunch& L, int op, uint32_t grid
   if (L.nbytes == 0) return hipSuccess;
   if (((uintptr_t)L.out & 15u) != 0) return hipErrorInvalidValue;
   // op 0 of a wide digest compares the slots' tails and records each hit's tail
-  if (op == 0 && L.algo >= A5X_ALGO_SHA1 && (!L.hit_tail || !L.tails)) return hipErrorInvalidValue;
+  if (op == 0 && a5x_algo_wide(L.algo) && (!L.hit_tail || !L.tails)) return hipErrorInvalidValue;
   const u64 nblk = a5x_digest_blocks(L.nbytes, L.algo);
   const u64 want = (nblk + 3) / 4;
   const u32 g = (u32)(want < grid ? want : grid);
@@ -389,6 +429,8 @@ hipError_t a5x_launch_digest_stream(const A5xDigLaunch& L, int op, uint32_t grid
     hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA384>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
   else if (L.algo == A5X_ALGO_SHA512)
     hipLaunchKernelGGL(k_digest_stream<A5X_ALGO_SHA512>, dim3(g), dim3(256), a5x_digest_lds(L.algo), st, L, op);
+  else if (a5x_algo_nested(L.algo))
+    return a5x_launch_digest_stream_nest(L, op, g, st);
   else
     return hipErrorInvalidValue;  // a missing kernel is an error, never another algorithm's digest
   return hipGetLastError();
@@ -406,3 +448,4 @@ hipError_t a5x_launch_hits_resolve(A5xHitRaw* hits, uint32_t n, const uint64_t* 
                      blk_pre, cand_base, cand_off, nw);
   return hipGetLastError();
 }
+#endif  // A5X_DIGEST_NEST

@@ -30,6 +30,7 @@
 #include "a5x_gosem.h"
 #include "a5x_launch.h"
 #include "a5x_md.h"
+#include "a5x_nest.h"
 #include "a5x_rules.h"
 #include "a5x_salt.h"
 #include "a5x_sha.h"
@@ -1291,17 +1292,13 @@ A5xDigLaunch dig_launch(a5x_ctx* c) {
 }
 
 // digest bytes per algorithm (a5x_digest_size), 0: not an algorithm
-inline uint32_t algo_size(int algo) {
-  switch (algo) {
-    case A5X_ALGO_MD5: case A5X_ALGO_NTLM: return 16u;
-    case A5X_ALGO_SHA1: return 20u;
-    case A5X_ALGO_SHA256: return 32u;
-    case A5X_ALGO_SHA224: return 28u;
-    case A5X_ALGO_SHA384: return 48u;
-    case A5X_ALGO_SHA512: return 64u;
-    default: return 0u;  // (4 is unassigned)
-  }
-}
+inline uint32_t algo_size(int algo) { return 4u * a5x_algo_words(algo); }  // (4, 8 and 9..15 are unassigned)
+// no salted mode: NTLM and the nested algorithms
+inline bool algo_unsalted(int algo) { return algo == A5X_ALGO_NTLM || a5x_algo_nested(algo); }
+// the fused expansion kernel that hashes a narrow plain algorithm (a5x_launch_expand's kind):
+// k_expand_fast_md5 / k_expand_fast_ntlm; -1: none (wide and nested sets never get here,
+// expand_digest sends them to the two-pass route)
+inline int fused_kind(int algo) { return algo == A5X_ALGO_MD5 ? 3 : algo == A5X_ALGO_NTLM ? 5 : -1; }
 
 // the context's sorted unique wide digests, in place
 template <size_t W>
@@ -1486,6 +1483,9 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
     allow_fused = false;
     c->t_hit_tails.clear();
   }
+  // a nested set (a5x_nest.h): the two-pass range loop in every mode too.  An MD5-outer one is
+  // not wide, and the fused kernels would hash it as plain MD5 / NTLM
+  if (a5x_algo_nested(c->t_algo) || fused_kind(c->t_algo) < 0) allow_fused = false;
   // rules loaded: the two-pass range loop too, k_rules_stream in place of k_digest_stream op 0
   const bool ruled = c->n_rules != 0;
   if (ruled) allow_fused = false;
@@ -1544,7 +1544,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
         E.dg_bitmap = D.bitmap; E.dg_bm_mask = D.bm_mask; E.dg_has_zero = D.has_zero_target;
         E.dg_table = D.table; E.dg_tmask = D.tmask;
         E.dg_hits = c->dg_hits.p; E.dg_hit_cap = (uint32_t)dev_hits; E.dg_nhits = c->d_scalars + 8;
-        HIPCHK(c, a5x_launch_expand(E, c->t_algo == A5X_ALGO_MD5 ? 3 : 5, J.st));
+        HIPCHK(c, a5x_launch_expand(E, fused_kind(c->t_algo), J.st));
       }
       HIPCHK(c, hipEventRecord(c->ev[2], J.st));
       HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, J.st));
@@ -1594,7 +1594,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       E.dg_hits = c->dg_hits.p; E.dg_hit_cap = (uint32_t)dev_hits; E.dg_nhits = c->d_scalars + 8;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 8, 0, 4, J.st));
       HIPCHK(c, hipEventRecord(c->ev[1], J.st));
-      HIPCHK(c, a5x_launch_expand(E, c->t_algo == A5X_ALGO_MD5 ? 3 : 5, J.st));
+      HIPCHK(c, a5x_launch_expand(E, fused_kind(c->t_algo), J.st));
       HIPCHK(c, hipEventRecord(c->ev[2], J.st));
       HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, J.st));
       HIPCHK(c, hipStreamSynchronize(J.st));
@@ -2647,7 +2647,7 @@ int a5x_set_salted_targets(a5x_ctx* c, int algo, int order, const uint8_t* dig, 
                            const uint64_t* salt_off) {
   if (!c) return A5X_E_ARG;
   const uint32_t W = algo_size(algo);  // digest bytes
-  if (!W || algo == A5X_ALGO_NTLM) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
+  if (!W || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
   if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS)
     return fail(c, A5X_E_ARG, "salt order %d: 0 is pass.salt, 1 is salt.pass", order);
   if (n && (!dig || !salt_off)) return fail(c, A5X_E_ARG, "null digests or salt offsets");
@@ -2738,7 +2738,7 @@ int a5x_load_salted_hashes(a5x_ctx* c, int algo, int order, const uint8_t* text,
                            uint64_t* n_targets, uint64_t* n_salts, uint64_t* n_skipped) {
   if (!c || (len && !text)) return A5X_E_ARG;
   const uint32_t W = algo_size(algo);
-  if (!W || algo == A5X_ALGO_NTLM) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
+  if (!W || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
   auto hexv = [](uint8_t ch) -> int {
     return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1;
   };
@@ -2823,7 +2823,7 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
                                    uint8_t* d_dig, uint64_t cap, uint64_t* n_lines, void* stream) {
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || (nbytes && !d_lines)) return A5X_E_ARG;
-  if (!algo_size(algo) || algo == A5X_ALGO_NTLM) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
+  if (!algo_size(algo) || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
   if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) return fail(c, A5X_E_ARG, "bad salt order %d", order);
   if (!c->salted || !c->n_salts) return fail(c, A5X_E_ARG, "no salted target set (a5x_set_salted_targets)");
   if (((uintptr_t)d_lines & 15u) != 0) return fail(c, A5X_E_ARG, "d_lines must be 16-byte aligned");
@@ -2876,57 +2876,10 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
   return decode_dev_err(c, c->h_scalars[2]);
 }
 
-// RFC 1321 compression on the host (the device core, a5x_md.h, is device code): the message
-// words come from the same padded-source loop the kernels' md5_src runs
-extern "C++" {
-static void md5_block_host(uint32_t* st, const uint32_t* M) {
-  static const uint32_t K[64] = {
-      0xd76aa478u, 0xe8c7b756u, 0x242070dbu, 0xc1bdceeeu, 0xf57c0fafu, 0x4787c62au, 0xa8304613u, 0xfd469501u,
-      0x698098d8u, 0x8b44f7afu, 0xffff5bb1u, 0x895cd7beu, 0x6b901122u, 0xfd987193u, 0xa679438eu, 0x49b40821u,
-      0xf61e2562u, 0xc040b340u, 0x265e5a51u, 0xe9b6c7aau, 0xd62f105du, 0x02441453u, 0xd8a1e681u, 0xe7d3fbc8u,
-      0x21e1cde6u, 0xc33707d6u, 0xf4d50d87u, 0x455a14edu, 0xa9e3e905u, 0xfcefa3f8u, 0x676f02d9u, 0x8d2a4c8au,
-      0xfffa3942u, 0x8771f681u, 0x6d9d6122u, 0xfde5380cu, 0xa4beea44u, 0x4bdecfa9u, 0xf6bb4b60u, 0xbebfbc70u,
-      0x289b7ec6u, 0xeaa127fau, 0xd4ef3085u, 0x04881d05u, 0xd9d4d039u, 0xe6db99e5u, 0x1fa27cf8u, 0xc4ac5665u,
-      0xf4292244u, 0x432aff97u, 0xab9423a7u, 0xfc93a039u, 0x655b59c3u, 0x8f0ccc92u, 0xffeff47du, 0x85845dd1u,
-      0x6fa87e4fu, 0xfe2ce6e0u, 0xa3014314u, 0x4e0811a1u, 0xf7537e82u, 0xbd3af235u, 0x2ad7d2bbu, 0xeb86d391u};
-  static const uint32_t R[16] = {7, 12, 17, 22, 5, 9, 14, 20, 4, 11, 16, 23, 6, 10, 15, 21};
-  uint32_t a = st[0], b = st[1], c = st[2], d = st[3];
-  for (uint32_t i = 0; i < 64; i++) {
-    uint32_t f, g;
-    if (i < 16) { f = (b & c) | (~b & d); g = i; }
-    else if (i < 32) { f = (d & b) | (~d & c); g = (5 * i + 1) & 15; }
-    else if (i < 48) { f = b ^ c ^ d; g = (3 * i + 5) & 15; }
-    else { f = c ^ (b | ~d); g = (7 * i) & 15; }
-    const uint32_t x = a + f + K[i] + M[g], s = R[(i >> 4) * 4 + (i & 3)];
-    a = d; d = c; c = b;
-    b += (x << s) | (x >> (32 - s));
-  }
-  st[0] += a; st[1] += b; st[2] += c; st[3] += d;
-}
-template <class S> static void md5_src_host(const S& src, uint32_t len, uint32_t* d) {
-  d[0] = 0x67452301u; d[1] = 0xefcdab89u; d[2] = 0x98badcfeu; d[3] = 0x10325476u;
-  const uint32_t nb = (len + 8u) / 64u + 1u;
-  for (uint32_t blk = 0; blk < nb; blk++) {
-    uint32_t M[16];
-    for (uint32_t j = 0; j < 16; j++) {
-      const uint32_t b = blk * 64u + 4u * j;
-      const int k = (int)len - (int)b;
-      const uint32_t raw = k > 0 ? src.at4(b) : 0u;
-      M[j] = (raw & rule_keep(k)) | ((k >= 0 && k < 4) ? (0x80u << (8 * k)) : 0u);
-    }
-    if (blk == nb - 1) {
-      M[14] = len << 3;
-      M[15] = len >> 29;
-    }
-    md5_block_host(d, M);
-  }
-}
-}  // extern "C++"
-
 int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t slen, const uint8_t* msg, size_t len,
                             uint8_t* out, size_t cap) {
   const uint32_t W = algo_size(algo);
-  if (!W || algo == A5X_ALGO_NTLM || (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) ||
+  if (!W || algo_unsalted(algo) || (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) ||
       (!salt && slen) || (!msg && len) || !out || slen > A5X_SALT_MAX)
     return A5X_E_ARG;
   if (cap < W) return A5X_E_CAPACITY;
@@ -2954,7 +2907,7 @@ int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t sle
     if (((const uint8_t*)w)[i]) return A5X_E_BOUNDS;
   uint32_t d[16];
   switch (algo) {
-    case A5X_ALGO_MD5: md5_src_host(b, L, d); break;
+    case A5X_ALGO_MD5: md5_src_hd(b, L, d); break;
     case A5X_ALGO_SHA1: sha_digest<A5X_ALGO_SHA1>(b, L, d); break;
     case A5X_ALGO_SHA256: sha_digest<A5X_ALGO_SHA256>(b, L, d); break;
     case A5X_ALGO_SHA224: sha_digest<A5X_ALGO_SHA224>(b, L, d); break;
@@ -3057,7 +3010,9 @@ int a5x_hit_digest(a5x_ctx* c, const a5x_hit* hit, uint8_t* out, size_t cap, siz
 }
 
 int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, size_t cap) {
-  if (algo < A5X_ALGO_SHA1 || !algo_size(algo) || (!msg && len) || !out || len > 0xffffff00u) return A5X_E_ARG;
+  // (MD5 and NTLM have no host core here: the kernels' are device code)
+  if (algo == A5X_ALGO_MD5 || algo == A5X_ALGO_NTLM || !algo_size(algo) || (!msg && len) || !out || len > 0xffffff00u)
+    return A5X_E_ARG;
   const uint32_t W = algo_size(algo);
   if (cap < W) return A5X_E_CAPACITY;
   ShaBytes src;
@@ -3069,7 +3024,15 @@ int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, siz
     case A5X_ALGO_SHA256: sha_digest<A5X_ALGO_SHA256>(src, (uint32_t)len, d); break;
     case A5X_ALGO_SHA224: sha_digest<A5X_ALGO_SHA224>(src, (uint32_t)len, d); break;
     case A5X_ALGO_SHA384: sha_digest<A5X_ALGO_SHA384>(src, (uint32_t)len, d); break;
-    default: sha_digest<A5X_ALGO_SHA512>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_SHA512: sha_digest<A5X_ALGO_SHA512>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_MD5_MD5: nest_digest<A5X_ALGO_MD5_MD5>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_MD5_MD5_MD5: nest_digest<A5X_ALGO_MD5_MD5_MD5>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_MD5_MD5UP: nest_digest<A5X_ALGO_MD5_MD5UP>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_MD5_SHA1: nest_digest<A5X_ALGO_MD5_SHA1>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_SHA1_SHA1: nest_digest<A5X_ALGO_SHA1_SHA1>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_SHA1_MD5: nest_digest<A5X_ALGO_SHA1_MD5>(src, (uint32_t)len, d); break;
+    case A5X_ALGO_SHA256_MD5: nest_digest<A5X_ALGO_SHA256_MD5>(src, (uint32_t)len, d); break;
+    default: return A5X_E_ARG;
   }
   memcpy(out, d, W);
   return A5X_OK;

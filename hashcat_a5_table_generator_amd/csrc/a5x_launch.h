@@ -268,13 +268,35 @@ struct A5xDigLaunch {
   // digest words past the first four of every table slot, the tails of the targets whose
   // first 16 bytes are zero (has_zero_target), and per hit the tail that matched, in hit
   // order at a stride of a5x_hit_tail_stride(algo) words: 4 for SHA-1 / SHA-256, 12 for
-  // SHA-224 / SHA-384 / SHA-512 (words past the algorithm's tail are zero)
+  // SHA-224 / SHA-384 / SHA-512 (words past the algorithm's tail are zero); the nested
+  // algorithms go by their outer digest's width (a5x_algo_words)
   const uint32_t* tails;
   const uint32_t* ztails;
   uint32_t nztails;
   uint32_t* hit_tail;
 };
-constexpr uint32_t a5x_hit_tail_stride(int algo) { return algo >= A5X_ALGO_SHA224 ? 12u : 4u; }
+// Kind and width of an algorithm value.  Every place that used to compare A5X_ALGO_* values
+// numerically asks these instead: the nested values (16..22) sort after SHA-512 whatever
+// their width.
+// a digest of the hex text of another digest (a5x_nest.h), 16 to 32 bytes wide
+constexpr bool a5x_algo_nested(int algo) { return algo >= A5X_ALGO_MD5_MD5 && algo <= A5X_ALGO_SHA256_MD5; }
+// 32-bit words of the digest (0: not an algorithm)
+constexpr uint32_t a5x_algo_words(int algo) {
+  return algo == A5X_ALGO_MD5 || algo == A5X_ALGO_NTLM ? 4u
+       : algo == A5X_ALGO_SHA1 ? 5u : algo == A5X_ALGO_SHA224 ? 7u : algo == A5X_ALGO_SHA256 ? 8u
+       : algo == A5X_ALGO_SHA384 ? 12u : algo == A5X_ALGO_SHA512 ? 16u
+       : algo == A5X_ALGO_MD5_MD5 || algo == A5X_ALGO_MD5_MD5_MD5 || algo == A5X_ALGO_MD5_MD5UP ||
+         algo == A5X_ALGO_MD5_SHA1 ? 4u
+       : algo == A5X_ALGO_SHA1_SHA1 || algo == A5X_ALGO_SHA1_MD5 ? 5u : algo == A5X_ALGO_SHA256_MD5 ? 8u : 0u;
+}
+// wider than the 16 bytes a table slot and a hit hold: tails compared and recorded
+constexpr bool a5x_algo_wide(int algo) { return a5x_algo_words(algo) > 4u; }
+// words of a hit's tail record, by digest width: 5 and 8 words (SHA-1, SHA-256 and the nested
+// forms with such an outer digest) 4; 7, 12 and 16 words (SHA-224 / SHA-384 / SHA-512) 12;
+// unused for a 4-word digest
+constexpr uint32_t a5x_hit_tail_stride(int algo) {
+  return a5x_algo_words(algo) == 7u || a5x_algo_words(algo) > 8u ? 12u : 4u;
+}
 size_t a5x_digest_lds(int algo);
 uint64_t a5x_digest_blocks(uint64_t nbytes, int algo);  // 2 KiB (NTLM) / 4 KiB (MD5, SHA-*) blocks
 hipError_t a5x_launch_digest_stream(const A5xDigLaunch& L, int op, uint32_t grid, hipStream_t st);

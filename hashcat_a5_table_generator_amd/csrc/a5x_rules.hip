@@ -21,6 +21,9 @@
 #include "a5x_md.h"
 #include "a5x_rules.h"
 #include "a5x_sha.h"
+#ifdef A5X_RULES_NEST
+#include "a5x_nest.h"
+#endif
 
 namespace {
 
@@ -37,8 +40,7 @@ static_assert(RMARGIN >= A5X_RULE_LMAX + 1u, "a rule-sized line that starts in a
 static_assert(A5X_RULE_NDW * 4u >= A5X_RULE_LMAX + 8u, "the hash sources read up to 8 bytes past the message");
 
 template <int ALGO> struct RCfg {
-  static constexpr u32 DW = ALGO == A5X_ALGO_SHA1 ? 5u : ALGO == A5X_ALGO_SHA256 ? 8u : ALGO == A5X_ALGO_SHA224 ? 7u
-                          : ALGO == A5X_ALGO_SHA384 ? 12u : ALGO == A5X_ALGO_SHA512 ? 16u : 4u;
+  static constexpr u32 DW = a5x_algo_words(ALGO);
   static constexpr u32 HT = a5x_hit_tail_stride(ALGO);  // words of a hit's tail record
   static_assert(DW <= 4u || DW - 4u <= HT, "the hit's tail record holds the whole tail");
 };
@@ -226,6 +228,9 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
         u32 d[DW];
         if constexpr (ALGO == A5X_ALGO_MD5) md5_src(buf, L, d);
         else if constexpr (ALGO == A5X_ALGO_NTLM) ntlm_stream(buf, L, d);
+#ifdef A5X_RULES_NEST
+        else if constexpr (a5x_algo_nested(ALGO)) nest_digest<ALGO>(buf, L, d);
+#endif
         else sha_digest<ALGO>(buf, L, d);
         if (op == 2) {
           if (valid) {
@@ -295,18 +300,34 @@ static hipError_t rules_launch(const A5xRuleLaunch& L, int op, uint32_t cus, hip
 // defined.  The compiler's inlining of the rule interpreter depends on how many kernels of a
 // module call it: with seven in one module the first four's code changed, in a module of their
 // own it is instruction-identical to what it was (DESIGN "SHA-224, SHA-384 and SHA-512").
-#ifndef A5X_RULES_WIDE
+// The seven nested algorithms (a5x_nest.h) have a third, a5x_rules_nest.hip (A5X_RULES_NEST).
+#if defined(A5X_RULES_NEST)
+// (arguments checked by a5x_launch_rules_stream)
+hipError_t a5x_launch_rules_stream_nest(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st) {
+  switch (L.d.algo) {
+    case A5X_ALGO_MD5_MD5: return rules_launch<A5X_ALGO_MD5_MD5>(L, op, cus, st);
+    case A5X_ALGO_MD5_MD5_MD5: return rules_launch<A5X_ALGO_MD5_MD5_MD5>(L, op, cus, st);
+    case A5X_ALGO_MD5_MD5UP: return rules_launch<A5X_ALGO_MD5_MD5UP>(L, op, cus, st);
+    case A5X_ALGO_MD5_SHA1: return rules_launch<A5X_ALGO_MD5_SHA1>(L, op, cus, st);
+    case A5X_ALGO_SHA1_SHA1: return rules_launch<A5X_ALGO_SHA1_SHA1>(L, op, cus, st);
+    case A5X_ALGO_SHA1_MD5: return rules_launch<A5X_ALGO_SHA1_MD5>(L, op, cus, st);
+    case A5X_ALGO_SHA256_MD5: return rules_launch<A5X_ALGO_SHA256_MD5>(L, op, cus, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+#elif !defined(A5X_RULES_WIDE)
 size_t a5x_rules_lds() { return RWAVES * ((sizeof(RWave) + 15u) & ~15u); }
 
 uint64_t a5x_rules_blocks(uint64_t nbytes) { return (nbytes + RBLK - 1) / RBLK; }
 
 hipError_t a5x_launch_rules_stream_wide(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st);
+hipError_t a5x_launch_rules_stream_nest(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st);
 
 hipError_t a5x_launch_rules_stream(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st) {
   if (L.d.nbytes == 0) return hipSuccess;
   if (((uintptr_t)L.d.out & 15u) != 0) return hipErrorInvalidValue;
   if (op != 1 && (!L.rules || !L.nrules || !L.rejected)) return hipErrorInvalidValue;
-  if (op == 0 && (!L.hit_rule || (L.d.algo >= A5X_ALGO_SHA1 && (!L.d.hit_tail || !L.d.tails)))) return hipErrorInvalidValue;
+  if (op == 0 && (!L.hit_rule || (a5x_algo_wide(L.d.algo) && (!L.d.hit_tail || !L.d.tails)))) return hipErrorInvalidValue;
   switch (L.d.algo) {
     case A5X_ALGO_MD5: return rules_launch<A5X_ALGO_MD5>(L, op, cus, st);
     case A5X_ALGO_NTLM: return rules_launch<A5X_ALGO_NTLM>(L, op, cus, st);
@@ -314,6 +335,9 @@ hipError_t a5x_launch_rules_stream(const A5xRuleLaunch& L, int op, uint32_t cus,
     case A5X_ALGO_SHA256: return rules_launch<A5X_ALGO_SHA256>(L, op, cus, st);
     case A5X_ALGO_SHA224: case A5X_ALGO_SHA384: case A5X_ALGO_SHA512:
       return a5x_launch_rules_stream_wide(L, op, cus, st);
+    case A5X_ALGO_MD5_MD5: case A5X_ALGO_MD5_MD5_MD5: case A5X_ALGO_MD5_MD5UP: case A5X_ALGO_MD5_SHA1:
+    case A5X_ALGO_SHA1_SHA1: case A5X_ALGO_SHA1_MD5: case A5X_ALGO_SHA256_MD5:
+      return a5x_launch_rules_stream_nest(L, op, cus, st);
     default: return hipErrorInvalidValue;  // a missing kernel is an error, never another algorithm's digest
   }
 }

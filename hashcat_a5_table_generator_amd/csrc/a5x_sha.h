@@ -13,7 +13,11 @@
 
 #include "a5x.h"
 
+#if defined(__HIPCC__) || defined(__CUDACC__)
 #define SHA_HD __host__ __device__ __forceinline__
+#else
+#define SHA_HD inline  // (a plain C++ build: tools/nest_selftest.cpp)
+#endif
 
 SHA_HD uint32_t sha_rotr(uint32_t x, uint32_t s) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -42,6 +42,14 @@ ALGO_SHA256 = 3  # FIPS 180-4 over the candidate bytes (hashcat -m 1400)
 ALGO_SHA224 = 5  # FIPS 180-4 over the candidate bytes (hashcat -m 1300)
 ALGO_SHA384 = 6  # FIPS 180-4 over the candidate bytes (hashcat -m 10800)
 ALGO_SHA512 = 7  # FIPS 180-4 over the candidate bytes (hashcat -m 1700)
+# (8..15 are unassigned) nested: a digest of the lower-case (UP: upper-case) hex text of another
+ALGO_MD5_MD5 = 16      # md5(hex(md5(p))) (hashcat -m 2600)
+ALGO_MD5_MD5_MD5 = 17  # md5(hex(md5(hex(md5(p))))) (hashcat -m 3500)
+ALGO_MD5_MD5UP = 18    # md5(HEX(md5(p))) (hashcat -m 4300)
+ALGO_MD5_SHA1 = 19     # md5(hex(sha1(p))) (hashcat -m 4400)
+ALGO_SHA1_SHA1 = 20    # sha1(hex(sha1(p))) (hashcat -m 4500)
+ALGO_SHA1_MD5 = 21     # sha1(hex(md5(p))) (hashcat -m 4700)
+ALGO_SHA256_MD5 = 22   # sha256(hex(md5(p))) (hashcat -m 20800)
 ORDER_PASS_SALT = 0  # salted sets: hash(candidate + salt), hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710
 ORDER_SALT_PASS = 1  # hash(salt + candidate), hashcat -m 20 / 120 / 1320 / 1420 / 10820 / 1720
 
@@ -50,7 +58,7 @@ SubMap = Dict[bytes, List[bytes]]
 
 def digest_size(algo: int) -> int:
     """Digest bytes of an algorithm (``a5x_digest_size``): 16, 16, 20, 32 for MD5, NTLM, SHA-1, SHA-256 and
-    28, 48, 64 for SHA-224, SHA-384, SHA-512."""
+    28, 48, 64 for SHA-224, SHA-384, SHA-512; the outer digest's 16, 20 or 32 for the nested algorithms."""
     n = _lib.load().a5x_digest_size(algo)
     if n < 0:
         raise A5xError(n, f"bad digest algorithm {algo}")

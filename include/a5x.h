@@ -61,8 +61,10 @@ enum {
   A5X_MODE_SUBALL_REVERSE = 3
 };
 
-/* digest algorithms of the fused digest + lookup stage.  Value 4 is
- * unassigned and invalid (A5X_E_ARG everywhere); additions never renumber. */
+/* digest algorithms of the fused digest + lookup stage.  Values 4, 8 and
+ * 9..15 are unassigned and invalid (A5X_E_ARG everywhere); additions never renumber.
+ * 16..22 are nested: a digest of the hex text of another digest, hex = lower-case ASCII
+ * hex of the inner digest in its standard byte order, HEX = upper-case. */
 enum {
   A5X_ALGO_MD5 = 0,   /* RFC 1321 over the candidate bytes (== Go crypto/md5); hashcat -m 0 */
   A5X_ALGO_NTLM = 1,  /* MD4 (RFC 1320) over UTF-16LE of the candidate ([]rune + utf16.Encode); -m 1000 */
@@ -70,10 +72,18 @@ enum {
   A5X_ALGO_SHA256 = 3, /* SHA-256 (FIPS 180-4) over the candidate bytes; hashcat -m 1400 */
   A5X_ALGO_SHA224 = 5, /* SHA-224 (FIPS 180-4) over the candidate bytes; hashcat -m 1300 */
   A5X_ALGO_SHA384 = 6, /* SHA-384 (FIPS 180-4) over the candidate bytes; hashcat -m 10800 */
-  A5X_ALGO_SHA512 = 7  /* SHA-512 (FIPS 180-4) over the candidate bytes; hashcat -m 1700 */
+  A5X_ALGO_SHA512 = 7, /* SHA-512 (FIPS 180-4) over the candidate bytes; hashcat -m 1700 */
+  A5X_ALGO_MD5_MD5 = 16,     /* md5(hex(md5(p))); hashcat -m 2600 */
+  A5X_ALGO_MD5_MD5_MD5 = 17, /* md5(hex(md5(hex(md5(p))))); hashcat -m 3500 */
+  A5X_ALGO_MD5_MD5UP = 18,   /* md5(HEX(md5(p))); hashcat -m 4300 */
+  A5X_ALGO_MD5_SHA1 = 19,    /* md5(hex(sha1(p))); hashcat -m 4400 */
+  A5X_ALGO_SHA1_SHA1 = 20,   /* sha1(hex(sha1(p))); hashcat -m 4500 */
+  A5X_ALGO_SHA1_MD5 = 21,    /* sha1(hex(md5(p))); hashcat -m 4700 */
+  A5X_ALGO_SHA256_MD5 = 22   /* sha256(hex(md5(p))); hashcat -m 20800 */
 };
-/* Digest bytes of an algorithm: 16, 16, 20, 32 for 0..3 and 28, 48, 64 for 5..7; A5X_E_ARG
- * for anything else (4 included).  Pure host function (no HIP call). */
+/* Digest bytes of an algorithm: 16, 16, 20, 32 for 0..3, 28, 48, 64 for 5..7 and 16, 16, 16,
+ * 16, 20, 20, 32 for 16..22 (the outer digest); A5X_E_ARG for anything else (4, 8 and 9..15
+ * included).  Pure host function (no HIP call). */
 A5X_API int a5x_digest_size(int algo);
 
 /* One target hit: word index in the batch, candidate index inside that word (in the
@@ -191,7 +201,9 @@ A5X_API int a5x_digest_device(a5x_ctx* ctx, const uint8_t* d_out, const uint64_t
  * a5x_digest_size(algo) bytes in the digest's standard byte order (duplicates allowed).
  * Built on the host (prefilter bitmap + open-addressing table keyed on the first 16
  * bytes, the remaining 4 to 48 bytes in a parallel array) and uploaded once.  For the wide
- * algorithms (SHA-1 and the SHA-2 family) the context keeps a host copy of the digests for a5x_hit_digest. */
+ * algorithms (SHA-1 and the SHA-2 family) the context keeps a host copy of the digests for a5x_hit_digest.
+ * A nested algorithm (16..22) takes its outer digests: 16, 20 or 32 bytes, wide when over 16.  A nested set
+ * is hashed by the two-pass route in every mode, with or without rules; it has no salted form. */
 A5X_API int a5x_set_targets(a5x_ctx* ctx, int algo, const uint8_t* digests, uint64_t n);
 /* The full digest of a hit against the context's current target set, *out_len =
  * a5x_digest_size of the set's algorithm (at most 64): the hit's own 16 bytes for MD5 /
@@ -239,7 +251,8 @@ A5X_API int a5x_format_plain(const uint8_t* plain, size_t len, uint8_t* out, siz
 /* One "hexdigest:plain\n" line per hit, in hit order, through sink (hashcat -m 0 /
  * -m 1000 / -m 100 / -m 1400 / -m 1300 / -m 10800 / -m 1700 potfile form, README.MD:74-106;
  * the full-width digest, 40 / 64 / 56 / 96 / 128 hex digits for SHA-1 / SHA-256 / SHA-224 /
- * SHA-384 / SHA-512, obtained as in a5x_hit_digest): the plains are
+ * SHA-384 / SHA-512, obtained as in a5x_hit_digest; a nested algorithm's outer digest, the
+ * potfile form of -m 2600 / 3500 / 4300 / 4400 / 4500 / 4700 / 20800): the plains are
  * regenerated on the device from the hit's (word, cand) with the same batch (host
  * buffers), mode and limits the hits were found with. */
 A5X_API int a5x_format_hits(a5x_ctx* ctx, const uint8_t* words, const uint64_t* word_off, uint64_t n_words,
@@ -286,7 +299,8 @@ A5X_API int a5x_debug_apply_rule(const uint8_t* rule, size_t rule_len, const uin
  * 10810 / 10820 (SHA-384), 1710 / 1720 (SHA-512)) ------------------------------------ */
 /* Replace the target set with a salted one: n digests of algo as in a5x_set_targets, target i
  * registered with the salt salt_bytes[salt_off[i] .. salt_off[i+1]) (n + 1 offsets; at most 64
- * bytes, 0 allowed: the unsalted digest).  order 0: the message is candidate + salt
+ * bytes, 0 allowed: the unsalted digest; the nested algorithms 16..22 have no salted form
+ * here: A5X_E_ARG, from every salted entry point).  order 0: the message is candidate + salt
  * (pass.salt), order 1: salt + candidate (salt.pass).  Salts are deduplicated; a salt's index
  * is its first appearance in the caller's order.  While the set is salted every
  * a5x_expand_digest* call hashes each candidate once per distinct salt, and a digest computed
@@ -402,8 +416,10 @@ A5X_API int a5x_debug_keyspace_stage(a5x_ctx* ctx, uint32_t* out);
 A5X_API int a5x_debug_keyspace_large_stage(a5x_ctx* ctx, int on);
 
 /* Test hook (CPU test suite): the digest of msg[0, len) computed on the host by the
- * __host__ __device__ core the digest kernels run (a5x_sha.h; SHA-1 and the SHA-2 family),
- * a5x_digest_size(algo) bytes into out.  Never called by a compute path. */
+ * __host__ __device__ core the digest kernels run (a5x_sha.h: SHA-1 and the SHA-2 family;
+ * a5x_nest.h: the nested algorithms 16..22), a5x_digest_size(algo) bytes into out.
+ * A5X_E_ARG for MD5 and NTLM (their cores are device code) and for every unassigned value.
+ * Never called by a compute path. */
 A5X_API int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, size_t cap);
 
 /* ---- device memory helpers (so hosts without torch can drive the API) ---------- */
