@@ -19,14 +19,11 @@
 // compacts them into an ordered start list, and every lane hashes one candidate at a
 // time; the candidate owned by a block is the one STARTING in it.  A hit records
 // (block, ordinal in block, digest); a per-block start count + scan turns that into
-// the global candidate index afterwards (hits are rare).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// the global candidate index afterwards (hits are rare).  The geometry, the wave
+// scan and the hit record are a5x_stream.h's, shared with the rules and salt kernels.
+#include "a5x_stream.h"
 
-#include "a5x.h"
 #include "a5x_format.h"
-#include "a5x_launch.h"
-#include "a5x_md.h"
 #include "a5x_sha.h"
 #ifdef A5X_DIGEST_NEST
 #include "a5x_nest.h"
@@ -34,39 +31,19 @@
 
 namespace {
 
-typedef uint64_t u64;
-typedef uint32_t u32;
-
 // stream bytes per wave: 4 KiB for MD5 (lanes stay busy over ~3 rounds of candidates),
 // 2 KiB for NTLM (the MD4 of UTF-16LE costs about twice per candidate byte), 4 KiB for
 // the SHA algorithms: their time is the hash rounds, and a block's last round of 64 lanes is
 // only part full -- C5's ~23-byte lines give 2 rounds per 2 KiB block, the second 40 %
 // full, against 3 rounds (the third 80 % full) per 4 KiB block; measured on C5 the digest
 // pass takes 83.4 vs 97.3 ms (SHA-1) and 132.4 vs 161.7 ms (SHA-256) at 4 vs 2 KiB
-// (profiles/r07_ab_sha_stream_block.json); DW = 32-bit words of the digest
+// (profiles/r07_ab_sha_stream_block.json)
 #ifndef A5X_SHA_DBLK
 #define A5X_SHA_DBLK 4096u  // (A/B knob: 2048u or 4096u)
 #endif
 template <int ALGO> struct DCfg {
   static constexpr u32 BLK = ALGO == A5X_ALGO_MD5 ? 4096u : (ALGO == A5X_ALGO_NTLM ? 2048u : A5X_SHA_DBLK);
-  static constexpr u32 DW = a5x_algo_words(ALGO);
-  static constexpr u32 HT = a5x_hit_tail_stride(ALGO);  // words of a hit's tail record
-  static_assert(DW <= 4u || DW - 4u <= HT, "the hit's tail record holds the whole tail");
 };
-constexpr u32 DMARGIN = 256;               // next-block bytes staged for straddling lines
-constexpr u32 D_ERR_HITCAP = 1u << 10;     // more hits than the caller's buffer
-
-__device__ __forceinline__ u32 d_lane() { return __lane_id(); }
-
-__device__ __forceinline__ u32 d_incl_scan(u32 x) {
-  const u32 lane = d_lane();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u32 y = (u32)__shfl_up((int)x, d, 64);
-    if ((int)lane >= d) x += y;
-  }
-  return x;
-}
 
 __device__ __forceinline__ u32 glob4(const uint8_t* base, u64 off, u64 lim) {
   u32 v = 0;
@@ -83,44 +60,8 @@ struct MdGlob {
   __device__ __forceinline__ u32 at4(u32 i) const { return glob4(g, off + i, lim); }
 };
 
-// Merkle-Damgard over message bytes [0, len) of src (LDS, or global when lds == false):
-// RFC 1321/1320 padding (0x80, zeros, 64-bit little-endian bit length).
-template <bool MD5>
-__device__ __forceinline__ void md_digest(const uint8_t* lbase, u32 loff, const uint8_t* gbase, u64 goff, u64 glim,
-                                          bool lds, u32 len, u32* st) {
-  st[0] = 0x67452301u; st[1] = 0xefcdab89u; st[2] = 0x98badcfeu; st[3] = 0x10325476u;
-  const u32 nb = (len + 8u) / 64u + 1u;
-  for (u32 blk = 0; blk < nb; blk++) {
-    u32 M[16];
-#pragma unroll
-    for (u32 j = 0; j < 16; j++) {
-      const u32 b = blk * 64u + 4u * j;
-      const int k = (int)len - (int)b;
-      u32 raw = 0;
-      if (k > 0) raw = lds ? lds4(lbase, loff + b) : glob4(gbase, goff + b, glim);
-      const u32 keep = k >= 4 ? 0xffffffffu : (k <= 0 ? 0u : ((1u << (8 * k)) - 1u));
-      const u32 pad = (k >= 0 && k < 4) ? (0x80u << (8 * k)) : 0u;
-      M[j] = (raw & keep) | pad;
-    }
-    if (blk == nb - 1) {
-      M[14] = len << 3;
-      M[15] = len >> 29;
-    }
-    if (MD5) md5_block(st, M); else md4_block(st, M);
-  }
-}
-
-__device__ __forceinline__ bool probe(const A5xDigLaunch& a, const u32* d) {
-  return md_probe(a.bitmap, a.bm_mask, a.table, a.tmask, a.has_zero_target != 0, d);
-}
-template <int TW>
-__device__ __forceinline__ bool probe_wide(const A5xDigLaunch& a, const u32* d) {
-  return md_probe_wide<TW>(a.bitmap, a.bm_mask, a.table, a.tails, a.tmask, a.has_zero_target != 0, a.ztails,
-                           a.nztails, d);
-}
-
-// message bytes of a line for sha_digest: the staged LDS bytes, or HBM for a line that
-// runs past them (the switch md_digest makes per word)
+// message bytes of a line for md_src, sha_digest and nest_digest: the staged LDS bytes, or HBM
+// for a line that runs past them
 struct ShaLine {
   const uint8_t* lbase;
   u32 loff;
@@ -132,8 +73,7 @@ struct ShaLine {
 
 template <u32 BLK>
 struct DWave {
-  static constexpr u32 BUF = BLK + DMARGIN + 80;  // + slack for the 8-B over-reads of the loader
-  uint8_t data[BUF];
+  uint8_t data[STREAM_BUF<BLK>];
   uint16_t starts[BLK + 2];
 };
 
@@ -143,13 +83,13 @@ template <int ALGO>
 __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
   static_assert(DCfg<ALGO>::BLK == 2048u || DCfg<ALGO>::BLK == 4096u, "a5x_digest_lds sizes these two");
   extern __shared__ __attribute__((aligned(16))) uint8_t d_dyn[];
-  const u32 wv = threadIdx.x / 64, lane = d_lane();
+  const u32 wv = threadIdx.x / 64, lane = __lane_id();
   const u32 nwv = blockDim.x / 64;
   constexpr u32 DBLK = DCfg<ALGO>::BLK;
-  constexpr u32 DW = DCfg<ALGO>::DW;
-  constexpr u32 HT = DCfg<ALGO>::HT;
+  constexpr u32 DW = StreamCfg<ALGO>::DW;
+  constexpr u32 HT = StreamCfg<ALGO>::HT;
   typedef DWave<DBLK> WT;
-  constexpr u32 DBUF = WT::BUF;
+  constexpr u32 DBUF = STREAM_BUF<DBLK>;
   constexpr u32 NM = DBLK / 2048u;  // 32-bit newline masks per lane (32 B each)
   const u32 per = (u32)sizeof(WT);
   WT& W = *(WT*)(d_dyn + wv * ((per + 15u) & ~15u));
@@ -158,7 +98,7 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
   for (u64 blk = (u64)blockIdx.x * nwv + wv; blk < nblk; blk += (u64)gridDim.x * nwv) {
     const u64 bs = blk * DBLK;
     const u32 bl = (u32)min<u64>(DBLK, a.nbytes - bs);                  // block bytes
-    const u32 sl = (u32)min<u64>(DBLK + DMARGIN, a.nbytes - bs);        // staged bytes
+    const u32 sl = (u32)min<u64>(DBLK + STREAM_MARGIN, a.nbytes - bs);        // staged bytes
     __builtin_amdgcn_wave_barrier();
     // stage [bs, bs + sl) (16-B loads; the stream base is 16-B aligned, see the launcher)
     const uint4* g16 = (const uint4*)(a.out + bs);
@@ -195,7 +135,7 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
       sm[h] = ((nl[h] << 1) | (h ? (nl[h - 1] >> 31) : carry)) & keep(q0 + 32u * h);
       m += (u32)__builtin_popcount(sm[h]);
     }
-    const u32 incl = d_incl_scan(m);
+    const u32 incl = wave_incl_scan(m);
     const u32 nst = (u32)__builtin_amdgcn_readlane((int)incl, 63);
     u32 o = incl - m;
 #pragma unroll
@@ -207,7 +147,7 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
     u64 tail_end = 0;
     if (nst) {
       const u32 s_last = W.starts[nst - 1];
-      const u32 lim = min(sl, DBLK + DMARGIN);
+      const u32 lim = min(sl, DBLK + STREAM_MARGIN);
       // lanes look at 64 consecutive bytes at a time
       u64 found = ~0ull;
       for (u32 base = s_last; base < lim && found == ~0ull; base += 64) {
@@ -239,22 +179,16 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
       // over-read of the last message word inside the buffer
       const bool in_lds = e <= sl && e + 8 <= DBUF;
       u32 d[DW];
-      if constexpr (ALGO == A5X_ALGO_MD5) {
-        md_digest<true>(W.data, s, a.out, bs + s, a.nbytes, in_lds, len, d);
+      if constexpr (ALGO != A5X_ALGO_NTLM) {
+        ShaLine src;
+        src.lbase = W.data; src.loff = s;
+        src.gbase = a.out; src.goff = bs + s; src.glim = a.nbytes;
+        src.lds = in_lds;
+        if constexpr (ALGO == A5X_ALGO_MD5) md_src<true>(src, len, d);
 #ifdef A5X_DIGEST_NEST
-      } else if constexpr (a5x_algo_nested(ALGO)) {
-        ShaLine src;
-        src.lbase = W.data; src.loff = s;
-        src.gbase = a.out; src.goff = bs + s; src.glim = a.nbytes;
-        src.lds = in_lds;
-        nest_digest<ALGO>(src, len, d);
+        else if constexpr (a5x_algo_nested(ALGO)) nest_digest<ALGO>(src, len, d);
 #endif
-      } else if constexpr (DW > 4) {
-        ShaLine src;
-        src.lbase = W.data; src.loff = s;
-        src.gbase = a.out; src.goff = bs + s; src.glim = a.nbytes;
-        src.lds = in_lds;
-        sha_digest<ALGO>(src, len, d);
+        else sha_digest<ALGO>(src, len, d);
       } else if (in_lds) {  // any length: the UTF-16LE units are made as MD4 blocks fill
         MdLds src;
         src.base = W.data;
@@ -278,23 +212,15 @@ __global__ void __launch_bounds__(256) k_digest_stream(A5xDigLaunch a, int op) {
           for (u32 k = 0; k < DW; k++) o1[k] = d[k];
         }
       } else if constexpr (DW == 4) {
-        hit = probe(a, d);
+        hit = md_probe(a.bitmap, a.bm_mask, a.table, a.tmask, a.has_zero_target != 0, d);
       } else {
-        hit = probe_wide<(int)DW - 4>(a, d);
+        hit = md_probe_wide<(int)DW - 4>(a.bitmap, a.bm_mask, a.table, a.tails, a.tmask, a.has_zero_target != 0, a.ztails,
+                                         a.nztails, d);
       }
       if (hit) {
         const u32 h = atomicAdd(a.nhits, 1u);
-        if (h < a.hit_cap) {
-          A5xHitRaw r;
-          r.blk = blk; r.idx = i; r.d[0] = d[0]; r.d[1] = d[1]; r.d[2] = d[2]; r.d[3] = d[3];
-          a.hits[h] = r;
-          if constexpr (DW > 4) {
-#pragma unroll
-            for (u32 k = 0; k < HT; k++) a.hit_tail[(u64)HT * h + k] = k < DW - 4 ? d[4 + k] : 0u;
-          }
-        } else {
-          err |= D_ERR_HITCAP;
-        }
+        if (h < a.hit_cap) stream_write_hit<DW, HT, false>(a.hits, a.hit_tail, h, blk, i, d, nullptr, 0u);
+        else err |= STREAM_ERR_HITCAP;
       }
     }
   }

@@ -1425,23 +1425,68 @@ int hit_full_digest(a5x_ctx* c, const a5x_hit* h, uint8_t* out) {
 
 uint32_t dig_grid(a5x_ctx* c) { return (uint32_t)std::max(1, c->cus) * 8u; }
 
-// per-2KiB-block line starts and their exclusive scan (blk_pre, nblk+1 entries)
-int dig_block_prefix(a5x_ctx* c, A5xDigLaunch& D, hipStream_t st, uint64_t* total_lines) {
+// Line starts per stream block and their exclusive scan (dg_blk_pre, nblk + 1 entries), for any
+// of the three stream kernels: launch_op1() runs the route's op 1 into dg_blk_cnt, which is
+// grown here first.  lines (null: not wanted): the stream's line count, read back.
+template <class F>
+int stream_count_lines(a5x_ctx* c, F launch_op1, uint64_t nblk, hipStream_t st, uint64_t* lines) {
   int rc;
-  const uint64_t nblk = a5x_digest_blocks(D.nbytes, D.algo);
   if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
       (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)))
     return rc;
-  D.blk_cnt = c->dg_blk_cnt.p;
-  HIPCHK(c, a5x_launch_digest_stream(D, 1, dig_grid(c), st));
+  HIPCHK(c, launch_op1());
   HIPCHK(c, a5x_launch_scan(c->dg_blk_cnt.p, c->dg_blk_cnt.p, nblk, c->dg_blk_pre.p, c->dg_blk_pre.p, c->scan_tmp.p,
                             c->d_scalars + 2, st));
-  D.blk_pre = c->dg_blk_pre.p;
-  if (total_lines) {
+  if (lines) {
     HIPCHK(c, hipMemcpyAsync(c->h_totals + 2, c->dg_blk_pre.p + nblk, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    *total_lines = c->h_totals[2];
+    *lines = c->h_totals[2];
   }
+  return A5X_OK;
+}
+
+// the plain route's: D.blk_cnt / D.blk_pre set for op 2 and the hit resolve
+int dig_block_prefix(a5x_ctx* c, A5xDigLaunch& D, hipStream_t st, uint64_t* total_lines) {
+  auto op1 = [&] {
+    D.blk_cnt = c->dg_blk_cnt.p;
+    return a5x_launch_digest_stream(D, 1, dig_grid(c), st);
+  };
+  const int rc = stream_count_lines(c, op1, a5x_digest_blocks(D.nbytes, D.algo), st, total_lines);
+  D.blk_pre = c->dg_blk_pre.p;
+  return rc;
+}
+
+// a5x_digest_lines_rules_device / a5x_digest_lines_salted_device behind their argument checks:
+// op 1, the capacity check for per_line digests a line, op 2, and the route's device counter
+// (r_counter, grown by the caller) read back into *counter.  Q holds the route's own fields,
+// Q.d is filled here; launch(op) runs the route's kernel on Q.
+template <class L, class F>
+int digest_lines_multi(a5x_ctx* c, L& Q, F launch, int algo, const uint8_t* d_lines, uint64_t nbytes, uint8_t* d_dig,
+                       uint64_t cap, uint32_t per_line, const char* unit, uint64_t* n_lines, hipStream_t st,
+                       uint64_t* lines, unsigned long long* counter) {
+  int rc;
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 64, st));
+  HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, st));
+  Q.d = dig_launch(c);
+  Q.d.algo = algo;
+  Q.d.out = d_lines;
+  Q.d.nbytes = nbytes;
+  auto op1 = [&] {
+    Q.d.blk_cnt = c->dg_blk_cnt.p;
+    return launch(1);
+  };
+  if ((rc = stream_count_lines(c, op1, a5x_stream_blocks(nbytes), st, lines))) return rc;
+  if (n_lines) *n_lines = *lines;
+  if (*lines > cap / per_line || !d_dig)
+    return fail(c, A5X_E_CAPACITY, "%llu lines x %u %s, digest buffer has room for %llu", (unsigned long long)*lines,
+                per_line, unit, (unsigned long long)cap);
+  Q.d.blk_cnt = nullptr;
+  Q.d.blk_pre = c->dg_blk_pre.p;
+  Q.d.dig_out = d_dig;
+  HIPCHK(c, launch(2));
+  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(counter, c->r_counter.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   return A5X_OK;
 }
 
@@ -1696,8 +1741,23 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
   const uint32_t HT = a5x_hit_tail_stride(c->t_algo);  // tail words the kernels record per hit
   if (wide && (rc = grow(c, c->dg_hit_tail, (uint64_t)HT * dev_hits))) return rc;
-  if (ruled && ((rc = grow(c, c->dg_hit_rule, dev_hits)) || (rc = grow(c, c->r_counter, 2)))) return rc;
-  if (salted && ((rc = grow(c, c->dg_hit_salt, dev_hits)) || (rc = grow(c, c->r_counter, 2)))) return rc;
+  // The route, chosen here once: the rule / salt index of every hit (device array beside the hit
+  // buffer, and the context's copy), and below the launch of the route's op 0 kernel
+  DevBuf<uint32_t>* const side = ruled ? &c->dg_hit_rule : salted ? &c->dg_hit_salt : nullptr;
+  std::vector<uint32_t>& side_host = ruled ? c->r_hit_rule : c->s_hit_salt;
+  if (side && ((rc = grow(c, *side, dev_hits)) || (rc = grow(c, c->r_counter, 2)))) return rc;
+  auto launch_op0 = [&](const A5xDigLaunch& D) -> hipError_t {
+    const uint32_t cus = (uint32_t)std::max(1, c->cus);
+    if (ruled) {
+      const A5xRuleLaunch RL = {D, c->r_table.p, c->n_rules, side->p, c->r_counter.p};
+      return a5x_launch_rules_stream(RL, 0, cus, J.st);
+    }
+    if (salted) {  // (an empty salted set has no salt to hash under: no launch, no hit)
+      const A5xSaltLaunch SL = {D, c->s_table.p, c->n_salts, c->s_order, side->p, c->r_counter.p};
+      return c->n_salts ? a5x_launch_salt_stream(SL, 0, cus, J.st) : hipSuccess;
+    }
+    return a5x_launch_digest_stream(D, 0, dig_grid(c), J.st);
+  };
   std::vector<uint32_t> htail;  // wide: the range's hit tails
   a5x_stats total;
   memset(&total, 0, sizeof total);
@@ -1716,7 +1776,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
     A5xDigLaunch D = dig_launch(c);
     D.out = c->dg_scratch.p;
     D.nbytes = R.b1 - R.b0;
-    const uint64_t nblk = ruled ? a5x_rules_blocks(D.nbytes) : salted ? a5x_salt_blocks(D.nbytes) : a5x_digest_blocks(D.nbytes, D.algo);
+    const uint64_t nblk = side ? a5x_stream_blocks(D.nbytes) : a5x_digest_blocks(D.nbytes, D.algo);
     if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
         (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)))
       return rc;
@@ -1735,32 +1795,12 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       D.hit_cap = (uint32_t)dev_hits;
       D.nhits = c->d_scalars + 8;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 8, 0, 4, J.st));
-      if (ruled || salted) HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, J.st));
+      if (side) HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, J.st));
       HIPCHK(c, hipEventRecord(c->dev_ev[0], J.st));
-      if (salted) {
-        A5xSaltLaunch SL;
-        SL.d = D;
-        SL.salts = c->s_table.p;
-        SL.nsalts = c->n_salts;
-        SL.order = c->s_order;
-        SL.hit_salt = c->dg_hit_salt.p;
-        SL.skipped = c->r_counter.p;
-        // (an empty salted set has no salt to hash under: no launch, no hit)
-        if (c->n_salts) HIPCHK(c, a5x_launch_salt_stream(SL, 0, (uint32_t)std::max(1, c->cus), J.st));
-      } else if (ruled) {
-        A5xRuleLaunch RL;
-        RL.d = D;
-        RL.rules = c->r_table.p;
-        RL.nrules = c->n_rules;
-        RL.hit_rule = c->dg_hit_rule.p;
-        RL.rejected = c->r_counter.p;
-        HIPCHK(c, a5x_launch_rules_stream(RL, 0, (uint32_t)std::max(1, c->cus), J.st));
-      } else {
-        HIPCHK(c, a5x_launch_digest_stream(D, 0, dig_grid(c), J.st));
-      }
+      HIPCHK(c, launch_op0(D));
       HIPCHK(c, hipEventRecord(c->dev_ev[1], J.st));
       HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, J.st));
-      if (ruled || salted) HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, J.st));
+      if (side) HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, J.st));
       HIPCHK(c, hipStreamSynchronize(J.st));
       float md = 0;
       HIPCHK(c, hipEventElapsedTime(&md, c->dev_ev[0], c->dev_ev[1]));
@@ -1772,8 +1812,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       dev_hits = nh;  // grow and run this range's digest again (its candidates are still in scratch)
       if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
       if (wide && (rc = grow(c, c->dg_hit_tail, (uint64_t)HT * dev_hits))) return rc;
-      if (ruled && (rc = grow(c, c->dg_hit_rule, dev_hits))) return rc;
-      if (salted && (rc = grow(c, c->dg_hit_salt, dev_hits))) return rc;
+      if (side && (rc = grow(c, *side, dev_hits))) return rc;
       HIPCHK(c, hipMemsetAsync(c->d_scalars + 2, 0, 4, J.st));
     }
     if (salted) {
@@ -1800,13 +1839,9 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
         htail.resize(HT * take);
         HIPCHK(c, hipMemcpyAsync(htail.data(), c->dg_hit_tail.p, take * 4 * HT, hipMemcpyDeviceToHost, J.st));
       }
-      if (take && ruled) {
-        c->r_hit_rule.resize(copied + take);
-        HIPCHK(c, hipMemcpyAsync(c->r_hit_rule.data() + copied, c->dg_hit_rule.p, take * 4, hipMemcpyDeviceToHost, J.st));
-      }
-      if (take && salted) {
-        c->s_hit_salt.resize(copied + take);
-        HIPCHK(c, hipMemcpyAsync(c->s_hit_salt.data() + copied, c->dg_hit_salt.p, take * 4, hipMemcpyDeviceToHost, J.st));
+      if (take && side) {
+        side_host.resize(copied + take);
+        HIPCHK(c, hipMemcpyAsync(side_host.data() + copied, side->p, take * 4, hipMemcpyDeviceToHost, J.st));
       }
       HIPCHK(c, hipStreamSynchronize(J.st));
       if (take && c->t_shared_prefix)  // (which of the targets sharing a prefix each hit matched: a5x_hit_digest)
@@ -2835,41 +2870,19 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
   c->s_hit_salt.clear();
   if (!nbytes) return A5X_OK;
   int rc;
-  const uint64_t nblk = a5x_salt_blocks(nbytes);
-  if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
-      (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)) || (rc = grow(c, c->r_counter, 2)))
-    return rc;
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 64, st));
-  HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, st));
+  if ((rc = grow(c, c->r_counter, 2))) return rc;
   A5xSaltLaunch SL;
-  SL.d = dig_launch(c);
-  SL.d.algo = algo;
-  SL.d.out = d_lines;
-  SL.d.nbytes = nbytes;
-  SL.d.blk_cnt = c->dg_blk_cnt.p;
   SL.salts = c->s_table.p;
   SL.nsalts = c->n_salts;
   SL.order = order;
   SL.hit_salt = nullptr;
   SL.skipped = c->r_counter.p;
-  HIPCHK(c, a5x_launch_salt_stream(SL, 1, (uint32_t)std::max(1, c->cus), st));
-  HIPCHK(c, a5x_launch_scan(c->dg_blk_cnt.p, c->dg_blk_cnt.p, nblk, c->dg_blk_pre.p, c->dg_blk_pre.p, c->scan_tmp.p,
-                            c->d_scalars + 2, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_totals + 2, c->dg_blk_pre.p + nblk, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const uint64_t lines = c->h_totals[2];
-  if (n_lines) *n_lines = lines;
-  if (lines > cap / c->n_salts || !d_dig)
-    return fail(c, A5X_E_CAPACITY, "%llu lines x %u salts, digest buffer has room for %llu", (unsigned long long)lines,
-                c->n_salts, (unsigned long long)cap);
-  SL.d.blk_cnt = nullptr;
-  SL.d.blk_pre = c->dg_blk_pre.p;
-  SL.d.dig_out = d_dig;
-  HIPCHK(c, a5x_launch_salt_stream(SL, 2, (uint32_t)std::max(1, c->cus), st));
+  auto launch = [&](int op) { return a5x_launch_salt_stream(SL, op, (uint32_t)std::max(1, c->cus), st); };
+  uint64_t lines = 0;
   unsigned long long skp = 0;
-  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(&skp, c->r_counter.p, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  if ((rc = digest_lines_multi(c, SL, launch, algo, d_lines, nbytes, d_dig, cap, c->n_salts, "salts", n_lines, st, &lines,
+                               &skp)))
+    return rc;
   if (skp > lines * c->n_salts) return fail(c, A5X_E_HIP, "more skipped pairs than pairs");
   c->s_skipped = skp;
   c->s_hashed = lines * c->n_salts - skp;
@@ -3359,40 +3372,18 @@ int a5x_digest_lines_rules_device(a5x_ctx* c, int algo, const uint8_t* d_lines, 
   c->r_hit_rule.clear();
   if (!nbytes) return A5X_OK;
   int rc;
-  const uint64_t nblk = a5x_rules_blocks(nbytes);
-  if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
-      (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)) || (rc = grow(c, c->r_counter, 2)))
-    return rc;
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 64, st));
-  HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, st));
+  if ((rc = grow(c, c->r_counter, 2))) return rc;
   A5xRuleLaunch RL;
-  RL.d = dig_launch(c);
-  RL.d.algo = algo;
-  RL.d.out = d_lines;
-  RL.d.nbytes = nbytes;
-  RL.d.blk_cnt = c->dg_blk_cnt.p;
   RL.rules = c->r_table.p;
   RL.nrules = c->n_rules;
   RL.hit_rule = nullptr;
   RL.rejected = c->r_counter.p;
-  HIPCHK(c, a5x_launch_rules_stream(RL, 1, (uint32_t)std::max(1, c->cus), st));
-  HIPCHK(c, a5x_launch_scan(c->dg_blk_cnt.p, c->dg_blk_cnt.p, nblk, c->dg_blk_pre.p, c->dg_blk_pre.p, c->scan_tmp.p,
-                            c->d_scalars + 2, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_totals + 2, c->dg_blk_pre.p + nblk, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const uint64_t lines = c->h_totals[2];
-  if (n_lines) *n_lines = lines;
-  if (lines > cap / c->n_rules || !d_dig)
-    return fail(c, A5X_E_CAPACITY, "%llu lines x %u rules, digest buffer has room for %llu", (unsigned long long)lines,
-                c->n_rules, (unsigned long long)cap);
-  RL.d.blk_cnt = nullptr;
-  RL.d.blk_pre = c->dg_blk_pre.p;
-  RL.d.dig_out = d_dig;
-  HIPCHK(c, a5x_launch_rules_stream(RL, 2, (uint32_t)std::max(1, c->cus), st));
+  auto launch = [&](int op) { return a5x_launch_rules_stream(RL, op, (uint32_t)std::max(1, c->cus), st); };
+  uint64_t lines = 0;
   unsigned long long rej = 0;
-  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  if ((rc = digest_lines_multi(c, RL, launch, algo, d_lines, nbytes, d_dig, cap, c->n_rules, "rules", n_lines, st, &lines,
+                               &rej)))
+    return rc;
   if (rej > lines) return fail(c, A5X_E_HIP, "more rejected lines than lines");
   c->r_rejected = rej;
   c->r_hashed = (lines - rej) * c->n_rules;

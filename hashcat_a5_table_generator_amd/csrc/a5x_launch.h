@@ -317,8 +317,9 @@ struct A5xRuleLaunch {
   uint32_t* hit_rule;            // op 0: the rule index of hit h, beside d.hits
   unsigned long long* rejected;  // += lines longer than A5X_RULE_LMAX (hashed under no rule)
 };
-size_t a5x_rules_lds();
-uint64_t a5x_rules_blocks(uint64_t nbytes);
+// LDS of a workgroup and 4 KiB blocks of a stream, for this route and the salted one (a5x_stream.h)
+size_t a5x_stream_lds();
+uint64_t a5x_stream_blocks(uint64_t nbytes);
 // op 0: hash + probe every (line, rule); op 1: line starts per block (d.blk_cnt); op 2: every
 // digest to d.dig_out at index line * nrules + rule (a rejected line's are zero)
 // (cus: the device's compute units; the grid is cus x the workgroups a CU holds at once)
@@ -333,8 +334,6 @@ struct A5xSaltLaunch {
   uint32_t* hit_salt;           // op 0: the public salt index of hit h, beside d.hits
   unsigned long long* skipped;  // += (line, salt) pairs whose message would exceed A5X_RULE_LMAX (not hashed)
 };
-size_t a5x_salt_lds();
-uint64_t a5x_salt_blocks(uint64_t nbytes);
 // op 0: hash + probe every (line, salt); op 1: line starts per block (d.blk_cnt); op 2: every
 // digest to d.dig_out at index line * nsalts + public salt index (a skipped pair's is zero)
 // (cus: the device's compute units; the grid is cus x the workgroups a CU holds at once)

@@ -189,9 +189,41 @@ __device__ __forceinline__ bool md_block_probe(const uint32_t* M, bool on, const
   return pass && md_probe(bitmap, bm_mask, table, tmask, has_zero, h);
 }
 
-// Merkle-Damgard over message bytes [off, off + len) of an LDS buffer (readable 8 bytes
-// past the message): RFC 1321 / 1320 padding (0x80, zeros, 64-bit little-endian bit
-// length); d = the 16-byte digest as 4 little-endian words.
+// Message byte sources of md_src and the UTF-16 walk: 4 bytes at message offset i (readable
+// past the message end).
+struct MdLds {  // LDS buffer, readable 8 bytes past the message
+  const uint8_t* base;
+  uint32_t off;
+  __device__ __forceinline__ uint32_t at4(uint32_t i) const { return lds4(base, off + i); }
+};
+
+// Merkle-Damgard over message bytes [0, len) of src (MD5, or MD4): RFC 1321 / 1320 padding
+// (0x80, zeros, 64-bit little-endian bit length); d = the 16-byte digest as 4 little-endian
+// words.  src.at4 is asked only for offsets below len, and the bytes past len are masked here.
+template <bool MD5, class S>
+__device__ __forceinline__ void md_src(const S& src, uint32_t len, uint32_t* d) {
+  d[0] = 0x67452301u; d[1] = 0xefcdab89u; d[2] = 0x98badcfeu; d[3] = 0x10325476u;
+  const uint32_t nb = (len + 8u) / 64u + 1u;
+  for (uint32_t blk = 0; blk < nb; blk++) {
+    uint32_t M[16];
+#pragma unroll
+    for (uint32_t j = 0; j < 16; j++) {
+      const uint32_t b = blk * 64u + 4u * j;
+      const int k = (int)len - (int)b;
+      const uint32_t raw = k > 0 ? src.at4(b) : 0u;
+      const uint32_t keep = k >= 4 ? 0xffffffffu : (k <= 0 ? 0u : ((1u << (8 * k)) - 1u));
+      const uint32_t pad = (k >= 0 && k < 4) ? (0x80u << (8 * k)) : 0u;
+      M[j] = (raw & keep) | pad;
+    }
+    if (blk == nb - 1) {
+      M[14] = len << 3;
+      M[15] = len >> 29;
+    }
+    if (MD5) md5_block(d, M); else md4_block(d, M);
+  }
+}
+// The fused kernels' form, the message at [off, off + len) of an LDS buffer.  It is md_src over an
+// MdLds written out: as a wrapper it changed the code of k_expand_fast_md5 and the mode kernels.
 template <bool MD5>
 __device__ __forceinline__ void md_lds(const uint8_t* base, uint32_t off, uint32_t len, uint32_t* d) {
   d[0] = 0x67452301u; d[1] = 0xefcdab89u; d[2] = 0x98badcfeu; d[3] = 0x10325476u;
@@ -214,14 +246,6 @@ __device__ __forceinline__ void md_lds(const uint8_t* base, uint32_t off, uint32
     if (MD5) md5_block(d, M); else md4_block(d, M);
   }
 }
-
-// Message byte sources for the UTF-16 walk: 4 bytes at message offset i (readable
-// past the message end).
-struct MdLds {  // LDS buffer, readable 4 bytes past the message
-  const uint8_t* base;
-  uint32_t off;
-  __device__ __forceinline__ uint32_t at4(uint32_t i) const { return lds4(base, off + i); }
-};
 
 // Next UTF-16 unit of Go's utf16.Encode([]rune(s)) over message bytes [0, len) of src:
 // i = byte position, pend = the pending low surrogate (0: none).  Invalid UTF-8 ->

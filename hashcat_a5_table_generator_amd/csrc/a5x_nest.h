@@ -12,7 +12,7 @@
 //   A5X_ALGO_SHA256_MD5   sha256(hex(md5(p)))         -m 20800
 //
 // Three stages, all in registers.  The inner digest is the length-generic core the plain
-// algorithms run (MD5: the padded-source loop of md5_src over md5_block; SHA-1: sha_digest),
+// algorithms run (MD5: the padded-source loop of md_src over md5_block; SHA-1: sha_digest),
 // over any source with at4().  Its words are turned into hex text two message words per digest
 // word: the word is split into its low and high nibbles (two AND, one shift), v_perm_b32
 // interleaves them straight into the byte order the outer compression reads -- little-endian
@@ -69,8 +69,8 @@ NEST_HD void md5_block_hd(uint32_t* st, const uint32_t* M) {
 
 // MD5 over message bytes [0, len) of src (src.at4(i) = the 4 bytes at message offset i as a
 // little-endian word; bytes past len are masked here): RFC 1321 padding (0x80, zeros, 64-bit
-// little-endian bit length); d = the digest as 4 little-endian words.  The loop of md5_src
-// (a5x_rules.hip) for host and device.
+// little-endian bit length); d = the digest as 4 little-endian words.  The loop of md_src
+// (a5x_md.h) for host and device.
 template <class S>
 NEST_HD void md5_src_hd(const S& src, uint32_t len, uint32_t* d) {
   d[0] = 0x67452301u; d[1] = 0xefcdab89u; d[2] = 0x98badcfeu; d[3] = 0x10325476u;
@@ -172,7 +172,7 @@ NEST_HD void nest_outer(const uint32_t* in, uint32_t* d) {
   }
 }
 
-// The nested digest ALGO of message bytes [0, len) of src (the source interface of md5_src /
+// The nested digest ALGO of message bytes [0, len) of src (the source interface of md_src /
 // sha_digest: src.at4(i)); d = the outer digest in its standard byte order as NestCfg<ALGO>::NW
 // little-endian words (what the target table is keyed on and what op 2 of k_digest_stream
 // stores).  The triple form repeats hex + block.

@@ -7,19 +7,10 @@
 // 64 candidates (lane = candidate) runs every rule: copy the candidate into the lane's
 // working buffer, interpret the rule's functions (a5x_rules.h; the function is the same for
 // all 64 lanes, so the interpreter's switch is a scalar branch), hash the ruled bytes, probe
-// the target set.  The block's HBM read is spread over R hashes.
-//
-// LDS per wave (RWave): 4432 B staged stream, 144 B round start list, 8704 B lane buffers
-// (34 dwords x 64 lanes, dword k of lane l at (k * 64 + l) * 4: a wave's access to dword k
-// touches 64 consecutive banks) = 13280 B; a 256-thread workgroup takes 53120 B, so three fit
-// the CU's 160 KiB: 12 waves, 3 on every SIMD (DESIGN "Rules").
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// the target set.  The block's HBM read is spread over R hashes.  The geometry, the LDS
+// layout, the lane buffer, the hit record and the launch are a5x_stream.h's.
+#include "a5x_stream.h"
 
-#include "a5x.h"
-#include "a5x_launch.h"
-#include "a5x_md.h"
-#include "a5x_rules.h"
 #include "a5x_sha.h"
 #ifdef A5X_RULES_NEST
 #include "a5x_nest.h"
@@ -27,109 +18,37 @@
 
 namespace {
 
-typedef uint64_t u64;
-typedef uint32_t u32;
-
-constexpr u32 RBLK = 4096;     // stream bytes per wave: C5's ~23-byte lines fill 3 rounds of 64 lanes to 93 %
-constexpr u32 RMARGIN = 256;   // next-block bytes staged for straddling lines
-constexpr u32 RWAVES = 4;      // waves per workgroup: one per SIMD, so a CU's resident workgroups load its SIMDs alike
-constexpr u32 R_ERR_HITCAP = 1u << 10;
-// a line that starts in the block and is at most A5X_RULE_LMAX bytes has its '\n' staged:
-// longer lines are rejected, so no line is ever read from HBM
-static_assert(RMARGIN >= A5X_RULE_LMAX + 1u, "a rule-sized line that starts in a block must end in the staged margin");
-static_assert(A5X_RULE_NDW * 4u >= A5X_RULE_LMAX + 8u, "the hash sources read up to 8 bytes past the message");
-
-template <int ALGO> struct RCfg {
-  static constexpr u32 DW = a5x_algo_words(ALGO);
-  static constexpr u32 HT = a5x_hit_tail_stride(ALGO);  // words of a hit's tail record
-  static_assert(DW <= 4u || DW - 4u <= HT, "the hit's tail record holds the whole tail");
-};
-
-struct RWave {
-  static constexpr u32 BUF = RBLK + RMARGIN + 80;  // + slack for the over-reads of the copy
-  uint8_t data[BUF];
-  uint16_t starts[72];              // the round's 64 line starts + the next one
-  u32 lanes[A5X_RULE_NDW * 64];     // working buffers, dword-interleaved
-};
-
-__device__ __forceinline__ u32 r_incl_scan(u32 x) {
-  const u32 lane = __lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u32 y = (u32)__shfl_up((int)x, d, 64);
-    if ((int)lane >= d) x += y;
-  }
-  return x;
-}
-
-// the lane's working buffer: dword k at lanes[k * 64 + lane]
-struct RLane {
-  u32* p;  // &lanes[lane]
-  __device__ __forceinline__ u32 rd(u32 k) const { return p[k * 64u]; }
-  __device__ __forceinline__ void wr(u32 k, u32 v) { p[k * 64u] = v; }
-  // message source of the digests: 4 bytes at message offset i (zero past the word)
-  __device__ __forceinline__ u32 at4(u32 i) const {
-    const u32 lo = p[(i >> 2) * 64u];
-    return (i & 3u) ? __builtin_amdgcn_alignbyte(p[((i >> 2) + 1u) * 64u], lo, i & 3u) : lo;
-  }
-};
-
-// MD5 over message bytes [0, len) of src (md_lds of a5x_md.h with a message source)
-template <class S>
-__device__ __forceinline__ void md5_src(const S& src, u32 len, u32* d) {
-  d[0] = 0x67452301u; d[1] = 0xefcdab89u; d[2] = 0x98badcfeu; d[3] = 0x10325476u;
-  const u32 nb = (len + 8u) / 64u + 1u;
-  for (u32 blk = 0; blk < nb; blk++) {
-    u32 M[16];
-#pragma unroll
-    for (u32 j = 0; j < 16; j++) {
-      const u32 b = blk * 64u + 4u * j;
-      const int k = (int)len - (int)b;
-      const u32 raw = k > 0 ? src.at4(b) : 0u;
-      const u32 keep = k >= 4 ? 0xffffffffu : (k <= 0 ? 0u : ((1u << (8 * k)) - 1u));
-      const u32 pad = (k >= 0 && k < 4) ? (0x80u << (8 * k)) : 0u;
-      M[j] = (raw & keep) | pad;
-    }
-    if (blk == nb - 1) {
-      M[14] = len << 3;
-      M[15] = len >> 29;
-    }
-    md5_block(d, M);
-  }
-}
-
 // op 0: every (candidate, rule) hashed and probed, hits recorded with their rule; op 1:
 // count line starts per block; op 2: every digest written at
 // dig_out[4 * DW * ((blk_pre[blk] + i) * R + r)], zeros for a rejected line
 template <int ALGO>
-__global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, int op) {
+__global__ void __launch_bounds__(64 * STREAM_WAVES) k_rules_stream(A5xRuleLaunch q, int op) {
   extern __shared__ __attribute__((aligned(16))) uint8_t r_dyn[];
   const A5xDigLaunch& a = q.d;
   const u32 wv = threadIdx.x / 64, lane = __lane_id();
   const u32 nwv = blockDim.x / 64;
-  constexpr u32 DW = RCfg<ALGO>::DW;
-  constexpr u32 HT = RCfg<ALGO>::HT;
-  constexpr u32 DBUF = RWave::BUF;
-  constexpr u32 NM = RBLK / 2048u;  // 32-bit newline masks per lane (32 B each)
+  constexpr u32 DW = StreamCfg<ALGO>::DW;
+  constexpr u32 HT = StreamCfg<ALGO>::HT;
+  constexpr u32 NM = STREAM_BLK / 2048u;  // 32-bit newline masks per lane (32 B each)
   static_assert(NM == 2, "a lane's starts are kept in one 64-bit mask");
-  RWave& W = *(RWave*)(r_dyn + wv * ((sizeof(RWave) + 15u) & ~15u));
-  RLane buf;
+  StreamWave& W = *(StreamWave*)(r_dyn + wv * ((sizeof(StreamWave) + 15u) & ~15u));
+  StreamLane buf;
   buf.p = W.lanes + lane;
   for (u32 k = 0; k < A5X_RULE_NDW; k++) buf.wr(k, 0u);
   u32 dirty = 0;  // dwords of the lane buffer that may be non-zero
-  const u64 nblk = (a.nbytes + RBLK - 1) / RBLK;
+  const u64 nblk = (a.nbytes + STREAM_BLK - 1) / STREAM_BLK;
   const u32 R = q.nrules;
   u32 err = 0, nrej = 0;
   for (u64 blk = (u64)blockIdx.x * nwv + wv; blk < nblk; blk += (u64)gridDim.x * nwv) {
-    const u64 bs = blk * RBLK;
-    const u32 bl = (u32)min<u64>(RBLK, a.nbytes - bs);             // block bytes
-    const u32 sl = (u32)min<u64>(RBLK + RMARGIN, a.nbytes - bs);   // staged bytes
+    const u64 bs = blk * STREAM_BLK;
+    const u32 bl = (u32)min<u64>(STREAM_BLK, a.nbytes - bs);             // block bytes
+    const u32 sl = (u32)min<u64>(STREAM_BLK + STREAM_MARGIN, a.nbytes - bs);   // staged bytes
     __builtin_amdgcn_wave_barrier();
     const uint4* g16 = (const uint4*)(a.out + bs);
     uint4* l16 = (uint4*)W.data;
     for (u32 i = lane; i < sl / 16; i += 64) l16[i] = g16[i];
     for (u32 i = (sl & ~15u) + lane; i < sl; i += 64) W.data[i] = a.out[bs + i];
-    for (u32 i = sl + lane; i < DBUF; i += 64) W.data[i] = 0;
+    for (u32 i = sl + lane; i < STREAM_BUF<STREAM_BLK>; i += 64) W.data[i] = 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -159,7 +78,7 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
       sm[h] = ((nl[h] << 1) | (h ? (nl[h - 1] >> 31) : carry)) & keep(q0 + 32u * h);
       m += (u32)__builtin_popcount(sm[h]);
     }
-    const u32 incl = r_incl_scan(m);
+    const u32 incl = wave_incl_scan(m);
     const u32 nst = (u32)__builtin_amdgcn_readlane((int)incl, 63);
     u32 ord = incl - m;  // ordinal of this lane's next unlisted start
     u64 sm64 = (u64)sm[0] | ((u64)sm[1] << 32);  // this lane's unlisted starts (bit = byte of its 64-B slice)
@@ -180,7 +99,7 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
         const u64 bal = __ballot(p < sl && W.data[p] == '\n');
         if (bal) tail_end = base + (u32)__builtin_ctzll(bal);
       }
-      if (tail_end == 0xffffffffu && sl < RBLK + RMARGIN) tail_end = sl;
+      if (tail_end == 0xffffffffu && sl < STREAM_BLK + STREAM_MARGIN) tail_end = sl;
     }
     for (u32 r0 = 0; r0 < nst; r0 += 64) {
       // the round's starts: every lane lists its own whose ordinal is in [r0, r0 + 64]
@@ -226,7 +145,7 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
         }
         dirty = act ? rule_ndw(L) : dirty;
         u32 d[DW];
-        if constexpr (ALGO == A5X_ALGO_MD5) md5_src(buf, L, d);
+        if constexpr (ALGO == A5X_ALGO_MD5) md_src<true>(buf, L, d);
         else if constexpr (ALGO == A5X_ALGO_NTLM) ntlm_stream(buf, L, d);
 #ifdef A5X_RULES_NEST
         else if constexpr (a5x_algo_nested(ALGO)) nest_digest<ALGO>(buf, L, d);
@@ -250,18 +169,8 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
         }
         if (hit) {
           const u32 h = atomicAdd(a.nhits, 1u);
-          if (h < a.hit_cap) {
-            A5xHitRaw hr;
-            hr.blk = blk; hr.idx = i; hr.d[0] = d[0]; hr.d[1] = d[1]; hr.d[2] = d[2]; hr.d[3] = d[3];
-            a.hits[h] = hr;
-            q.hit_rule[h] = r;
-            if constexpr (DW > 4) {
-#pragma unroll
-              for (u32 k = 0; k < HT; k++) a.hit_tail[(u64)HT * h + k] = k < DW - 4 ? d[4 + k] : 0u;
-            }
-          } else {
-            err |= R_ERR_HITCAP;
-          }
+          if (h < a.hit_cap) stream_write_hit<DW, HT, true>(a.hits, a.hit_tail, h, blk, i, d, q.hit_rule, r);
+          else err |= STREAM_ERR_HITCAP;
         }
       }
     }
@@ -270,30 +179,12 @@ __global__ void __launch_bounds__(64 * RWAVES) k_rules_stream(A5xRuleLaunch q, i
   if (err) atomicOr(a.err, err);
 }
 
-}  // namespace
-
-// grid and launch of one instantiation.  The grid is exactly the waves the device holds at
-// once (cus x resident workgroups): every wave takes the same share of the blocks in its
-// grid-stride loop.  A larger grid runs a second, part-empty residency round -- 16 waves per
-// CU launched against 12 resident cost 0.72-0.85 of the no-rule stream's hash rate where this
-// gives DESIGN "Rules"'s figures.
 template <int ALGO>
-static hipError_t rules_launch(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st) {
-  const u64 want = (a5x_rules_blocks(L.d.nbytes) + RWAVES - 1) / RWAVES;
-  const size_t lds = a5x_rules_lds();
-  // workgroups of k_rules_stream<ALGO> one CU holds at once (LDS: 3; fewer if the registers say so)
-  static int per_cu = 0;
-  if (!per_cu) {
-    int v = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_rules_stream<ALGO>, 64 * RWAVES, lds) != hipSuccess || v < 1)
-      v = 2;  // (2 waves per SIMD)
-    per_cu = v;
-  }
-  const u64 grid = (u64)(cus ? cus : 1u) * (u32)per_cu;
-  const u32 g = (u32)(want < grid ? want : grid);
-  hipLaunchKernelGGL(k_rules_stream<ALGO>, dim3(g), dim3(64 * RWAVES), lds, st, L, op);
-  return hipGetLastError();
+hipError_t rules_launch(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st) {
+  return stream_launch<k_rules_stream<ALGO>>(L, op, cus, st);
 }
+
+}  // namespace
 
 // The instantiations live in two translation units: MD5 / NTLM / SHA-1 / SHA-256 here, SHA-224
 // / SHA-384 / SHA-512 in a5x_rules_wide.hip, which includes this file with A5X_RULES_WIDE
@@ -316,9 +207,9 @@ hipError_t a5x_launch_rules_stream_nest(const A5xRuleLaunch& L, int op, uint32_t
   }
 }
 #elif !defined(A5X_RULES_WIDE)
-size_t a5x_rules_lds() { return RWAVES * ((sizeof(RWave) + 15u) & ~15u); }
+size_t a5x_stream_lds() { return STREAM_WAVES * ((sizeof(StreamWave) + 15u) & ~15u); }
 
-uint64_t a5x_rules_blocks(uint64_t nbytes) { return (nbytes + RBLK - 1) / RBLK; }
+uint64_t a5x_stream_blocks(uint64_t nbytes) { return (nbytes + STREAM_BLK - 1) / STREAM_BLK; }
 
 hipError_t a5x_launch_rules_stream_wide(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st);
 hipError_t a5x_launch_rules_stream_nest(const A5xRuleLaunch& L, int op, uint32_t cus, hipStream_t st);

@@ -12,66 +12,17 @@
 // per round and per salt only appends; salt.pass copies it once per run of salts of equal
 // length (the host sorts the salt table by length) and per salt only writes the salt's dwords.
 //
-// The front half (staging, SWAR newline scan, per-round start lists) is k_rules_stream's,
-// duplicated: those kernels stay as they are.  LDS per wave as there (13280 B; three
-// workgroups of four waves a CU).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// The front half (staging, SWAR newline scan, per-round start lists) is k_rules_stream's text;
+// the geometry, the LDS layout (three workgroups of four waves a CU), the lane buffer, the hit
+// record and the launch are a5x_stream.h's.
+#include "a5x_stream.h"
 
-#include "a5x.h"
-#include "a5x_launch.h"
-#include "a5x_md.h"
 #include "a5x_salt.h"
 #include "a5x_sha.h"
 
 namespace {
 
-typedef uint64_t u64;
-typedef uint32_t u32;
-
-constexpr u32 SBLK = 4096;     // stream bytes per wave (the rules kernel's block: k_hits_resolve's ordinals)
-constexpr u32 SMARGIN = 256;   // next-block bytes staged for straddling lines
-constexpr u32 SWAVES = 4;      // waves per workgroup: one per SIMD
-constexpr u32 S_ERR_HITCAP = 1u << 10;
-static_assert(SMARGIN >= A5X_RULE_LMAX + 1u, "a message-sized line that starts in a block must end in the staged margin");
-static_assert(A5X_RULE_NDW * 4u >= A5X_RULE_LMAX + 8u, "the hash sources read up to 8 bytes past the message");
 static_assert(A5X_SALT_STRIDE >= A5X_SALT_R_BYTES + A5X_SALT_MAX / 4u, "a salt record holds the whole salt");
-
-template <int ALGO> struct SCfg {
-  static constexpr u32 DW = ALGO == A5X_ALGO_SHA1 ? 5u : ALGO == A5X_ALGO_SHA256 ? 8u : ALGO == A5X_ALGO_SHA224 ? 7u
-                          : ALGO == A5X_ALGO_SHA384 ? 12u : ALGO == A5X_ALGO_SHA512 ? 16u : 4u;
-  static constexpr u32 HT = a5x_hit_tail_stride(ALGO);  // words of a hit's tail record
-  static_assert(DW <= 4u || DW - 4u <= HT, "the hit's tail record holds the whole tail");
-};
-
-struct SWave {
-  static constexpr u32 BUF = SBLK + SMARGIN + 80;  // + slack for the over-reads of the copy
-  uint8_t data[BUF];
-  uint16_t starts[72];              // the round's 64 line starts + the next one
-  u32 lanes[A5X_RULE_NDW * 64];     // working buffers, dword-interleaved
-};
-
-__device__ __forceinline__ u32 s_incl_scan(u32 x) {
-  const u32 lane = __lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u32 y = (u32)__shfl_up((int)x, d, 64);
-    if ((int)lane >= d) x += y;
-  }
-  return x;
-}
-
-// the lane's working buffer: dword k at lanes[k * 64 + lane] (whatever k: the bank is the lane)
-struct SLane {
-  u32* p;  // &lanes[lane]
-  __device__ __forceinline__ u32 rd(u32 k) const { return p[k * 64u]; }
-  __device__ __forceinline__ void wr(u32 k, u32 v) { p[k * 64u] = v; }
-  // message source of the digests: 4 bytes at message offset i (zero past the message)
-  __device__ __forceinline__ u32 at4(u32 i) const {
-    const u32 lo = p[(i >> 2) * 64u];
-    return (i & 3u) ? __builtin_amdgcn_alignbyte(p[((i >> 2) + 1u) * 64u], lo, i & 3u) : lo;
-  }
-};
 
 // the candidate in the staged stream: 4 bytes at candidate offset i (line starts are byte
 // aligned: funnel reads; the bytes past the candidate are masked by the placement)
@@ -81,63 +32,38 @@ struct SCand {
   __device__ __forceinline__ u32 at4(u32 i) const { return lds4(base, s + i); }
 };
 
-// MD5 over message bytes [0, len) of src (k_rules_stream's md5_src)
-template <class S>
-__device__ __forceinline__ void md5_src(const S& src, u32 len, u32* d) {
-  d[0] = 0x67452301u; d[1] = 0xefcdab89u; d[2] = 0x98badcfeu; d[3] = 0x10325476u;
-  const u32 nb = (len + 8u) / 64u + 1u;
-  for (u32 blk = 0; blk < nb; blk++) {
-    u32 M[16];
-#pragma unroll
-    for (u32 j = 0; j < 16; j++) {
-      const u32 b = blk * 64u + 4u * j;
-      const int k = (int)len - (int)b;
-      const u32 raw = k > 0 ? src.at4(b) : 0u;
-      const u32 keep = k >= 4 ? 0xffffffffu : (k <= 0 ? 0u : ((1u << (8 * k)) - 1u));
-      const u32 pad = (k >= 0 && k < 4) ? (0x80u << (8 * k)) : 0u;
-      M[j] = (raw & keep) | pad;
-    }
-    if (blk == nb - 1) {
-      M[14] = len << 3;
-      M[15] = len >> 29;
-    }
-    md5_block(d, M);
-  }
-}
-
 // op 0: every (candidate, salt) hashed and probed under the salt's mask, hits recorded with
 // their salt index; op 1: count line starts per block; op 2: every digest written at
 // dig_out[4 * DW * ((blk_pre[blk] + i) * S + salt index)], zeros for a skipped pair
 template <int ALGO>
-__global__ void __launch_bounds__(64 * SWAVES) k_salt_stream(A5xSaltLaunch q, int op) {
+__global__ void __launch_bounds__(64 * STREAM_WAVES) k_salt_stream(A5xSaltLaunch q, int op) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
   const A5xDigLaunch& a = q.d;
   const u32 wv = threadIdx.x / 64, lane = __lane_id();
   const u32 nwv = blockDim.x / 64;
-  constexpr u32 DW = SCfg<ALGO>::DW;
-  constexpr u32 HT = SCfg<ALGO>::HT;
-  constexpr u32 DBUF = SWave::BUF;
-  constexpr u32 NM = SBLK / 2048u;  // 32-bit newline masks per lane (32 B each)
+  constexpr u32 DW = StreamCfg<ALGO>::DW;
+  constexpr u32 HT = StreamCfg<ALGO>::HT;
+  constexpr u32 NM = STREAM_BLK / 2048u;  // 32-bit newline masks per lane (32 B each)
   static_assert(NM == 2, "a lane's starts are kept in one 64-bit mask");
-  SWave& W = *(SWave*)(s_dyn + wv * ((sizeof(SWave) + 15u) & ~15u));
-  SLane buf;
+  StreamWave& W = *(StreamWave*)(s_dyn + wv * ((sizeof(StreamWave) + 15u) & ~15u));
+  StreamLane buf;
   buf.p = W.lanes + lane;
   for (u32 k = 0; k < A5X_RULE_NDW; k++) buf.wr(k, 0u);
   u32 dirty = 0;  // dwords of the lane buffer that may be non-zero
-  const u64 nblk = (a.nbytes + SBLK - 1) / SBLK;
+  const u64 nblk = (a.nbytes + STREAM_BLK - 1) / STREAM_BLK;
   const u32 S = q.nsalts;
   const bool prefix = q.order == A5X_SALT_ORDER_SALT_PASS;
   u32 err = 0, nskip = 0;
   for (u64 blk = (u64)blockIdx.x * nwv + wv; blk < nblk; blk += (u64)gridDim.x * nwv) {
-    const u64 bs = blk * SBLK;
-    const u32 bl = (u32)min<u64>(SBLK, a.nbytes - bs);             // block bytes
-    const u32 sl = (u32)min<u64>(SBLK + SMARGIN, a.nbytes - bs);   // staged bytes
+    const u64 bs = blk * STREAM_BLK;
+    const u32 bl = (u32)min<u64>(STREAM_BLK, a.nbytes - bs);             // block bytes
+    const u32 sl = (u32)min<u64>(STREAM_BLK + STREAM_MARGIN, a.nbytes - bs);   // staged bytes
     __builtin_amdgcn_wave_barrier();
     const uint4* g16 = (const uint4*)(a.out + bs);
     uint4* l16 = (uint4*)W.data;
     for (u32 i = lane; i < sl / 16; i += 64) l16[i] = g16[i];
     for (u32 i = (sl & ~15u) + lane; i < sl; i += 64) W.data[i] = a.out[bs + i];
-    for (u32 i = sl + lane; i < DBUF; i += 64) W.data[i] = 0;
+    for (u32 i = sl + lane; i < STREAM_BUF<STREAM_BLK>; i += 64) W.data[i] = 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -167,7 +93,7 @@ __global__ void __launch_bounds__(64 * SWAVES) k_salt_stream(A5xSaltLaunch q, in
       sm[h] = ((nl[h] << 1) | (h ? (nl[h - 1] >> 31) : carry)) & keep(q0 + 32u * h);
       m += (u32)__builtin_popcount(sm[h]);
     }
-    const u32 incl = s_incl_scan(m);
+    const u32 incl = wave_incl_scan(m);
     const u32 nst = (u32)__builtin_amdgcn_readlane((int)incl, 63);
     u32 ord = incl - m;  // ordinal of this lane's next unlisted start
     u64 sm64 = (u64)sm[0] | ((u64)sm[1] << 32);  // this lane's unlisted starts (bit = byte of its 64-B slice)
@@ -188,7 +114,7 @@ __global__ void __launch_bounds__(64 * SWAVES) k_salt_stream(A5xSaltLaunch q, in
         const u64 bal = __ballot(p < sl && W.data[p] == '\n');
         if (bal) tail_end = base + (u32)__builtin_ctzll(bal);
       }
-      if (tail_end == 0xffffffffu && sl < SBLK + SMARGIN) tail_end = sl;
+      if (tail_end == 0xffffffffu && sl < STREAM_BLK + STREAM_MARGIN) tail_end = sl;
     }
     for (u32 r0 = 0; r0 < nst; r0 += 64) {
       // the round's starts: every lane lists its own whose ordinal is in [r0, r0 + 64]
@@ -237,7 +163,7 @@ __global__ void __launch_bounds__(64 * SWAVES) k_salt_stream(A5xSaltLaunch q, in
         }
         if (act) L = len + slen;
         u32 d[DW];
-        if constexpr (ALGO == A5X_ALGO_MD5) md5_src(buf, L, d);
+        if constexpr (ALGO == A5X_ALGO_MD5) md_src<true>(buf, L, d);
         else sha_digest<ALGO>(buf, L, d);
         const u32 sidx = rec.r[A5X_SALT_R_INDEX];
         if (op == 2) {
@@ -262,18 +188,8 @@ __global__ void __launch_bounds__(64 * SWAVES) k_salt_stream(A5xSaltLaunch q, in
         }
         if (hit) {
           const u32 h = atomicAdd(a.nhits, 1u);
-          if (h < a.hit_cap) {
-            A5xHitRaw hr;
-            hr.blk = blk; hr.idx = i; hr.d[0] = d[0]; hr.d[1] = d[1]; hr.d[2] = d[2]; hr.d[3] = d[3];
-            a.hits[h] = hr;
-            q.hit_salt[h] = sidx;
-            if constexpr (DW > 4) {
-#pragma unroll
-              for (u32 k = 0; k < HT; k++) a.hit_tail[(u64)HT * h + k] = k < DW - 4 ? d[4 + k] : 0u;
-            }
-          } else {
-            err |= S_ERR_HITCAP;
-          }
+          if (h < a.hit_cap) stream_write_hit<DW, HT, true>(a.hits, a.hit_tail, h, blk, i, d, q.hit_salt, sidx);
+          else err |= STREAM_ERR_HITCAP;
         }
       }
     }
@@ -282,37 +198,19 @@ __global__ void __launch_bounds__(64 * SWAVES) k_salt_stream(A5xSaltLaunch q, in
   if (err) atomicOr(a.err, err);
 }
 
-// grid and launch of one instantiation: exactly the workgroups the device holds at once
-// (cus x resident workgroups), every wave an equal share of the blocks, as rules_launch
 template <int ALGO>
 hipError_t salt_launch(const A5xSaltLaunch& L, int op, uint32_t cus, hipStream_t st) {
-  const u64 want = (a5x_salt_blocks(L.d.nbytes) + SWAVES - 1) / SWAVES;
-  const size_t lds = a5x_salt_lds();
-  static int per_cu = 0;  // workgroups of k_salt_stream<ALGO> one CU holds at once (LDS: 3; fewer if the registers say so)
-  if (!per_cu) {
-    int v = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_salt_stream<ALGO>, 64 * SWAVES, lds) != hipSuccess || v < 1)
-      v = 2;  // (2 waves per SIMD)
-    per_cu = v;
-  }
-  const u64 grid = (u64)(cus ? cus : 1u) * (u32)per_cu;
-  const u32 g = (u32)(want < grid ? want : grid);
-  hipLaunchKernelGGL(k_salt_stream<ALGO>, dim3(g), dim3(64 * SWAVES), lds, st, L, op);
-  return hipGetLastError();
+  return stream_launch<k_salt_stream<ALGO>>(L, op, cus, st);
 }
 
 }  // namespace
-
-size_t a5x_salt_lds() { return SWAVES * ((sizeof(SWave) + 15u) & ~15u); }
-
-uint64_t a5x_salt_blocks(uint64_t nbytes) { return (nbytes + SBLK - 1) / SBLK; }
 
 hipError_t a5x_launch_salt_stream(const A5xSaltLaunch& L, int op, uint32_t cus, hipStream_t st) {
   if (L.d.nbytes == 0) return hipSuccess;
   if (((uintptr_t)L.d.out & 15u) != 0) return hipErrorInvalidValue;
   if (L.order != A5X_SALT_ORDER_PASS_SALT && L.order != A5X_SALT_ORDER_SALT_PASS) return hipErrorInvalidValue;
   if (op != 1 && (!L.salts || !L.nsalts || !L.skipped)) return hipErrorInvalidValue;
-  if (op == 0 && (!L.hit_salt || (L.d.algo >= A5X_ALGO_SHA1 && (!L.d.hit_tail || !L.d.tails)))) return hipErrorInvalidValue;
+  if (op == 0 && (!L.hit_salt || (a5x_algo_wide(L.d.algo) && (!L.d.hit_tail || !L.d.tails)))) return hipErrorInvalidValue;
   switch (L.d.algo) {
     case A5X_ALGO_MD5: return salt_launch<A5X_ALGO_MD5>(L, op, cus, st);
     case A5X_ALGO_SHA1: return salt_launch<A5X_ALGO_SHA1>(L, op, cus, st);

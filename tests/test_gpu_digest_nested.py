@@ -22,8 +22,8 @@ CLI = os.path.join(ROOT, "hashcat_a5_table_generator_amd", "_build", "a5x_genera
 MD5 = 0
 MD5_MD5, MD5_MD5_MD5, MD5_MD5UP, MD5_SHA1, SHA1_SHA1, SHA1_MD5, SHA256_MD5 = range(16, 23)
 E_ARG, E_CAPACITY = -1, -8
-BLOCK = 4096   # DCfg<nested>::BLK of a5x_digest.hip, RBLK of a5x_rules.hip
-MARGIN = 256   # DMARGIN: next-block bytes staged in LDS
+BLOCK = 4096   # DCfg<nested>::BLK of a5x_digest.hip, STREAM_BLK of a5x_stream.h
+MARGIN = 256   # STREAM_MARGIN of a5x_stream.h: next-block bytes staged in LDS
 LMAX = 128
 
 

@@ -23,7 +23,7 @@ REF = {MD5: lambda b: hashlib.md5(b).digest(), NTLM: functools.lru_cache(maxsize
        SHA1: lambda b: hashlib.sha1(b).digest(), SHA256: lambda b: hashlib.sha256(b).digest()}
 SIZE = {MD5: 16, NTLM: 16, SHA1: 20, SHA256: 32}
 ALGOS = pytest.mark.parametrize("algo", [MD5, NTLM, SHA1, SHA256], ids=["md5", "ntlm", "sha1", "sha256"])
-RULES_BLOCK = 4096  # RBLK of a5x_rules.hip
+RULES_BLOCK = 4096  # STREAM_BLK of a5x_stream.h
 LMAX = 128
 
 # every function at least once; growth rules that carry the long lines (53..128 bytes) across

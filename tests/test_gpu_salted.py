@@ -26,7 +26,7 @@ IDS = {MD5: "md5", SHA1: "sha1", SHA256: "sha256", SHA224: "sha224", SHA384: "sh
 ALGOS = pytest.mark.parametrize("algo", sorted(REF), ids=[IDS[a] for a in sorted(REF)])
 TWO_ALGOS = pytest.mark.parametrize("algo", [MD5, SHA512], ids=["md5", "sha512"])
 ORDERS = pytest.mark.parametrize("order", [0, 1], ids=["pass.salt", "salt.pass"])
-BLOCK = 4096  # SBLK of a5x_salt.hip
+BLOCK = 4096  # STREAM_BLK of a5x_stream.h
 LMAX = 128
 E_CAPACITY = -8
 
