@@ -38,6 +38,7 @@ EXPORTS = (
     "a5x_format_hits_rules", "a5x_digest_lines_rules_device", "a5x_debug_apply_rule",
     "a5x_set_salted_targets", "a5x_load_salted_hashes", "a5x_salt_count", "a5x_salt_get", "a5x_hit_salts",
     "a5x_salts_last", "a5x_format_hits_salted", "a5x_digest_lines_salted_device", "a5x_debug_digest_salted",
+    "a5x_debug_target_set",
 )
 
 
@@ -155,6 +156,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     L.a5x_format_hits_salted.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, i, SINK, vp]
     L.a5x_digest_lines_salted_device.argtypes = [vp, i, i, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
     L.a5x_debug_digest_salted.argtypes = [i, i, ctypes.c_char_p, sz, ctypes.c_char_p, sz, vp, sz]
+    L.a5x_debug_target_set.argtypes = [u32, vp, u64, vp, vp, sz, vp, sz, vp, sz, vp, sz]
     _lib = L
     return L
 
@@ -166,3 +168,29 @@ def check(rc: int, ctx=None) -> None:
             m = load().a5x_last_error(ctx)
             msg = m.decode(errors="replace") if m else ""
         raise A5xError(rc, msg)
+
+
+def debug_target_set(width: int, digests: bytes) -> dict:
+    """The target set ``a5x_set_targets`` builds from ``digests`` (n * width bytes), as the
+    host lays it out before the upload (``a5x_debug_target_set``; a test hook, no context, no
+    device): ``bm_log2``, ``size`` (table slots), ``has_zero``, ``shared`` and the numpy
+    arrays ``table`` (size x 4 words), ``tails`` (size x (width / 4 - 4)), ``ztails`` (one row
+    per zero-prefix target) and ``bitmap`` (64-bit words)."""
+    import numpy as np
+    L = load()
+    digests = bytes(digests)
+    if width <= 0 or len(digests) % width:
+        raise A5xError(-1, f"{len(digests)} bytes are no whole number of {width}-byte digests")
+    n = len(digests) // width
+    src = np.frombuffer(digests + bytes(16), dtype=np.uint8)
+    info = np.zeros(8, dtype=np.uint64)
+    check(L.a5x_debug_target_set(width, src.ctypes.data, n, info.ctypes.data, None, 0, None, 0, None, 0, None, 0))
+    tw = width // 4 - 4
+    tab, tails, zt, bm = (np.zeros(max(1, int(k)), dtype=np.uint32) for k in info[4:8])
+    check(L.a5x_debug_target_set(width, src.ctypes.data, n, info.ctypes.data, tab.ctypes.data, len(tab),
+                                 tails.ctypes.data, len(tails), zt.ctypes.data, len(zt), bm.ctypes.data, len(bm)))
+    size = int(info[1])
+    return {"bm_log2": int(info[0]), "size": size, "has_zero": int(info[2]), "shared": int(info[3]),
+            "table": tab[: int(info[4])].reshape(size, 4), "tails": tails[: int(info[5])].reshape(size, tw) if tw else tails[:0].reshape(size, 0),
+            "ztails": zt[: int(info[6])].reshape(-1, tw) if tw else zt[:0].reshape(0, 0),
+            "bitmap": bm[: int(info[7])].view(np.uint64)}

@@ -3051,6 +3051,31 @@ int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, siz
   return A5X_OK;
 }
 
+int a5x_debug_target_set(uint32_t width, const uint8_t* dig, uint64_t n, uint64_t* info, uint32_t* table,
+                         size_t table_cap, uint32_t* tails, size_t tails_cap, uint32_t* ztails, size_t ztails_cap,
+                         uint32_t* bitmap, size_t bitmap_cap) {
+  const bool known = width == 16 || width == 20 || width == 28 || width == 32 || width == 48 || width == 64;
+  if (!known || (n && !dig) || !info) return A5X_E_ARG;
+  TargetSet T;
+  build_target_set(width, dig, n, T);
+  info[0] = T.bm_log2;
+  info[1] = T.tmask + 1;
+  info[2] = T.has_zero;
+  info[3] = T.shared ? 1 : 0;
+  info[4] = T.tab.size() * 4;
+  info[5] = T.tails.size();
+  info[6] = T.ztails.size();
+  info[7] = T.bm.size();
+  if (!table && !tails && !ztails && !bitmap) return A5X_OK;  // the size query
+  if (!table || !bitmap || (!tails && info[5]) || (!ztails && info[6])) return A5X_E_ARG;
+  if (table_cap < info[4] || tails_cap < info[5] || ztails_cap < info[6] || bitmap_cap < info[7]) return A5X_E_CAPACITY;
+  memcpy(table, T.tab.data(), T.tab.size() * sizeof(uint4));
+  if (info[5]) memcpy(tails, T.tails.data(), T.tails.size() * 4);
+  if (info[6]) memcpy(ztails, T.ztails.data(), T.ztails.size() * 4);
+  memcpy(bitmap, T.bm.data(), T.bm.size() * 4);
+  return A5X_OK;
+}
+
 int a5x_partition(const uint64_t* prefix, uint64_t n, uint32_t parts, uint64_t* split) {
   if (!prefix || !split || parts == 0) return A5X_E_ARG;
   const uint64_t total = prefix[n];

@@ -422,6 +422,19 @@ A5X_API int a5x_debug_keyspace_large_stage(a5x_ctx* ctx, int on);
  * Never called by a compute path. */
 A5X_API int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, size_t cap);
 
+/* Test hook (CPU test suite), pure host, no context: the target set a5x_set_targets builds
+ * and uploads (the same build_target_set) from n digests of `width` bytes (16, 20, 28, 32, 48
+ * or 64), copied out as 32-bit words.  info[8] = {bm_log2, table slots, has_zero, shared
+ * (two targets share their first 16 bytes), words of table (4 per slot), words of tails
+ * (width / 4 - 4 per slot), words of ztails (the tails of the zero-prefix targets), words of
+ * bitmap}.  All four buffers NULL: the size query, info only.  Otherwise table and bitmap,
+ * and tails / ztails where their size is not 0, must be given (A5X_E_ARG) with capacities in
+ * words of at least info[4..7] (A5X_E_CAPACITY; info is filled either way).  Honours
+ * A5X_TARGET_BM_LOG2.  Never called by a compute path. */
+A5X_API int a5x_debug_target_set(uint32_t width, const uint8_t* digests, uint64_t n, uint64_t* info, uint32_t* table,
+                                 size_t table_cap, uint32_t* tails, size_t tails_cap, uint32_t* ztails,
+                                 size_t ztails_cap, uint32_t* bitmap, size_t bitmap_cap);
+
 /* ---- device memory helpers (so hosts without torch can drive the API) ---------- */
 A5X_API int a5x_dev_alloc(a5x_ctx* ctx, void** p, size_t bytes);
 A5X_API int a5x_dev_free(a5x_ctx* ctx, void* p);

@@ -145,8 +145,10 @@ def test_lookup_with_a_full_32_bit_prefilter(gpu_ctx, monkeypatch):
     pl = [(w, len(per_word[w]) // 2) for w in range(0, 400, 13) if per_word[w]]
     gpu_ctx.set_targets(0, b"".join(dg.md5(per_word[w][c]) for w, c in pl))
     hits, _ = gpu_ctx.expand_digest(*pack_words(words), 0, 0, 15)
-    got = {(w, c) for w, c, _ in hits}
-    assert set(pl) <= got
+    tg = {dg.md5(per_word[w][c]) for w, c in pl}
+    want = {(w, c) for w, cs in enumerate(per_word) for c, x in enumerate(cs) if dg.md5(x) in tg}
+    assert set(pl) <= want
+    assert sorted((w, c) for w, c, _ in hits) == sorted(want)  # every planted candidate once, no false hit
 
 
 def test_fused_ntlm_multi_block_candidates(gpu_ctx):
