@@ -2626,6 +2626,20 @@ int a5x_debug_plan_sizes(a5x_ctx* c, const uint8_t* word, size_t len, uint32_t* 
   return A5X_OK;
 }
 
+int a5x_debug_piece_build(a5x_ctx* c, const uint8_t* word, size_t len, uint32_t* out) {
+  if (!c || !out || (!word && len)) return A5X_E_ARG;
+  if (len > 127) return fail(c, A5X_E_ARG, "word of %zu bytes (the piece builder's check takes <= 127)", len);
+  if (c->table.keys.empty()) return fail(c, A5X_E_NOTABLE, "no substitution table loaded");
+  if (c->table_dirty || c->blob.empty()) {
+    int rc = compile_table(c);
+    if (rc) return rc;
+  }
+  std::vector<uint8_t> wb(word, word + len);
+  wb.resize(len + 16, 0);
+  piece_build_compare(wb.data(), (u32)len, tab_view(c->blob.data()), out);
+  return A5X_OK;
+}
+
 // the context's salted state dropped: the target set (if any) is an unsalted one
 static void clear_salts(a5x_ctx* c) {
   c->salted = false;

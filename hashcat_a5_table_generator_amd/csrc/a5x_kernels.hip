@@ -293,8 +293,9 @@ __device__ __forceinline__ u32 wave_append(bool pred, u32* ctr) {
 
 #ifndef KS_ABL
 #define KS_ABL 0  // keyspace timing ablations (variant builds only, wrong output): 1 no build pass,
-                  // 4 no record stores (2, no planner in the count pass, is gone: the build pass
-                  // checks its plan against the count pass's, so it never gave a figure)
+                  // 4 no record stores, 8 the replayed words' cuts but no group entries (2, no
+                  // planner in the count pass, is gone: the build pass checks its plan against
+                  // the count pass's, so it never gave a figure)
 #endif
 
 // k_keyspace_thread's open group holds KS_GCAP entries (a unit with more choices
@@ -314,6 +315,12 @@ struct DevRecSink {
   __device__ void gst(u32, u32 a, u64 v) { g[a * 256u] = v; }
   __device__ void ent(u32 i, u64 v) { if (!(KS_ABL & 4)) rec[1 + np + i] = v; }
   __device__ void desc(u32 i, u64 v) { if (!(KS_ABL & 4)) rec[1 + i] = v; }
+};
+
+// A word's column of k_keyspace_thread's unit log (LDS; PieceBuilder's unit source).
+struct ULogCol {
+  const uint16_t* p;
+  __device__ __forceinline__ u32 operator()(u32 i) const { return p[i * 256u]; }
 };
 
 // A word's bytes staged in LDS (the keyspace tile); 8 readable bytes past any word.
@@ -766,31 +773,51 @@ __device__ __forceinline__ void ks_thread_tiles(const KsArgs& a) {
       u64* rec = a.rec + tile * FW_TILE_REC + ro;
       DevRecSink sk;
       sk.g = gbuf + tid; sk.c = sk.g; sk.rec = rec; sk.np = ff_np(f);  // no clusters here
-      Planner<true, LWord, DevRecSink, KS_GCAP> pb(lw, T, sk, build ? fb_balanced_cap(C.count + 1) : 0u);
-      CountAcc A2;
-      bool c2 = false;
-      // replay the logged units (no second byte walk); words with more units re-walk
+      // replay the logged units (no second byte walk): the cuts per unit, then every group's
+      // entries once per piece (PieceBuilder); words with more units re-walk
       const bool replay = nlog <= KS_ULOG;
-      const u32 nrep = build && replay ? nlog : 0u;
-      for (u32 i = 0; i < wave_max_u32((KS_ABL & 1) ? 0u : nrep); i++) {
-        if (i < nrep) {
-          const u32 e = ulog_c[i * 256u];
-          Unit U;
-          lone_unit(T, e >> 10, e & 1023u, U);
-          u64 seen = 0;
-          if (rm) (void)mode_unit(T, U, a.rmode, seen, false);  // (qualified in the count pass)
-          pb.unit(U);
+      const bool rebuild = build && replay && !(KS_ABL & 1);
+      {
+        const ULogCol lg{ulog_c};
+        PieceBuilder<LWord, DevRecSink, ULogCol, KS_GCAP> pc(lw, T, sk, lg);
+        const u32 nrep = rebuild ? nlog : 0u;
+        for (u32 i = 0; i < wave_max_u32(nrep); i++) {
+          if (i < nrep) {
+            const u32 e = ulog_c[i * 256u];
+            Unit U;
+            lone_unit(T, e >> 10, e & 1023u, U);
+            u64 seen = 0;
+            if (rm) (void)mode_unit(T, U, a.rmode, seen, false);  // (qualified in the count pass)
+            pc.unit(U);
+          }
+        }
+        if (rebuild) pc.finish(L);
+        const Plan& P = pc.P;
+        // (a group list of 8: np <= FW_PMAX for a FAST word, and a plan that disagrees with
+        // the count pass's is reported below whatever was built)
+        const u32 ngr = rebuild && P.ok && !(KS_ABL & 8) ? umin32(P.ng, 8u) : 0u;
+        for (u32 g = 0; g < wave_max_u32(ngr); g++)
+          if (g < ngr) pc.build_group(g, L);
+        if (rebuild) {
+          rec[0] = fr_hdr(P.np, P.ng, P.ne, P.maxl, P.nbig, P.bstarts, P.bRp);
+          if (!P.ok || P.ng != ff_ng(f) || P.ne != ff_ne(f) || P.np != ff_np(f)) atomicOr(a.err, A5X_DERR_STATE);
+          a.roff[w] = (u32)(tile * FW_TILE_REC + ro);
         }
       }
-      const bool walk = build && !replay;
-      if (!(KS_ABL & 1)) psk_walk<false, UTF>(lw, L, walk, wave_max_u32(walk ? L : 0u), bmax, T, pb, A2, c2, a.rmode);
-      if (build && !(KS_ABL & 1)) {
-        pb.finish(L);
-        pb.pick_balanced();
-        const Plan& P = pb.P;
-        rec[0] = fr_hdr(P.np, P.ng, P.ne, P.maxl, P.nbig, P.bstarts, P.bRp);
-        if (c2 || !P.ok || P.ng != ff_ng(f) || P.ne != ff_ne(f) || P.np != ff_np(f)) atomicOr(a.err, A5X_DERR_STATE);
-        a.roff[w] = (u32)(tile * FW_TILE_REC + ro);
+      const bool walk = build && !replay && !(KS_ABL & 1);
+      if (__builtin_amdgcn_ballot_w64(walk)) {
+        Planner<true, LWord, DevRecSink, KS_GCAP> pb(lw, T, sk, walk ? fb_balanced_cap(C.count + 1) : 0u);
+        CountAcc A2;
+        bool c2 = false;
+        psk_walk<false, UTF>(lw, L, walk, wave_max_u32(walk ? L : 0u), bmax, T, pb, A2, c2, a.rmode);
+        if (walk) {
+          pb.finish(L);
+          pb.pick_balanced();
+          const Plan& P = pb.P;
+          rec[0] = fr_hdr(P.np, P.ng, P.ne, P.maxl, P.nbig, P.bstarts, P.bRp);
+          if (c2 || !P.ok || P.ng != ff_ng(f) || P.ne != ff_ne(f) || P.np != ff_np(f)) atomicOr(a.err, A5X_DERR_STATE);
+          a.roff[w] = (u32)(tile * FW_TILE_REC + ro);
+        }
       }
     }
     if (fast && !build) {

@@ -678,6 +678,186 @@ struct CountPlanner {
   }
 };
 
+// fr_magic for the R of an 8-entry group, without the 32-bit division
+A5X_HD u32 fr_magic8(u32 R) {
+  u32 m = 0u;
+  m = R == 2 ? 0x80000000u : m; m = R == 3 ? 0x55555556u : m; m = R == 4 ? 0x40000000u : m;
+  m = R == 5 ? 0x33333334u : m; m = R == 6 ? 0x2AAAAAABu : m; m = R == 7 ? 0x24924925u : m;
+  m = R == 8 ? 0x20000000u : m;
+  return m;
+}
+
+// The build pass of k_keyspace_thread for words of lone units that come from a unit log
+// (LG: ul(i) = unit i as q << 10 | key): Planner<true, ., ., CAP> with the construction of a
+// group's entries taken out of the unit step.  Planner rewrites every entry of the open group
+// at every merge, through the sink's group buffer; but a closed group's entries are a function
+// of where its bytes start, its member units (<= 3: every R >= 2, CAP <= 8) and whether the
+// tail joined it.  unit() / finish() only decide -- the same cuts as Planner, straight-line
+// as in CountPlanner, with the header fields of big_join -- and leave one descriptor per group
+// in the sink's group buffer (gst(0, g, .), g < 8: a FAST word has <= FW_PMAX pieces):
+//   off | first unit << 7 | members << 15 | tail << 17 | first entry << 18 (10 bits) |
+//   (R - 1) of members 0..2 << 30 (3 bits each; 0 past the last member) | piece << 39
+// (the fields hold any word of <= 127 bytes with <= 8 groups, FAST or not: the host check)
+// build_group(g, L) then writes the group's entries and piece descriptor once, from
+// registers.  Literal pieces are written where they are cut, as Planner::literal does.
+// a5x_debug_piece_build / tests/test_plan_piece_build.py compare the records of the two.
+template <class W, class S, class LG, u32 CAP = 8>
+struct PieceBuilder {
+  static_assert(CAP <= 8, "<= 3 members of R >= 2, 3-bit R - 1 fields, fr_magic8");
+  const W& wd;
+  const Tab& T;
+  S& sk;
+  const LG& ul;
+  Plan P;             // lconst, minl stay 0
+  u32 bR, bl, bspan;  // the big piece being filled
+  u32 cR, cmax, prev; // cR = 0: no open group
+  u32 nu;             // units taken (the log index of the next)
+  u64 gd;             // the open group's descriptor
+
+  A5X_HD PieceBuilder(const W& w, const Tab& t, S& s, const LG& lg) : wd(w), T(t), sk(s), ul(lg) {
+    P.np = 0; P.ng = 0; P.ne = 0; P.lconst = 0; P.maxl = 0; P.minl = 0; P.ok = true;
+    P.nbig = 0; P.bstarts = 0; P.bent = 0; P.bRp = 0;
+    bR = 1; bl = 0; bspan = 0; cR = 0; cmax = 0; prev = 0; nu = 0; gd = 0;
+  }
+  // Planner::big_join (FB_RMAX) for a small piece pi that exists when c
+  A5X_HD void big(u32 R, u32 maxlen, u32 pi, bool c) {
+    const bool join = P.nbig && bl + maxlen <= FB_PLEN && bR * R <= FB_RMAX && bspan < FB_SPAN;
+    const bool fresh = c && !join;
+    const u32 nR = join ? bR * R : R;
+    P.bstarts |= fresh && P.nbig >= 1 && P.nbig <= 3 ? (pi & 7u) << ((3u * (P.nbig - 1u)) & 31u) : 0u;
+    P.nbig += fresh ? 1u : 0u;
+    P.bent += c ? (join ? nR - bR : R) : 0u;
+    bR = c ? nR : bR; bl = c ? (join ? bl + maxlen : maxlen) : bl; bspan = c ? (join ? bspan + 1u : 1u) : bspan;
+    const u32 sh = (6u * (P.nbig - 1u)) & 31u;
+    P.bRp = c && P.nbig >= 1 && P.nbig <= FB_NMAX ? (P.bRp & ~(63u << sh)) | (((bR - 1u) & 63u) << sh) : P.bRp;
+  }
+  A5X_HD void literal(u32 off, u32 n, bool nl_last) {  // Planner::literal
+    const u32 nb = nl_last ? n - 1 : n;
+    u64 v = nb ? wd.ld(off, nb) : 0ull;
+    if (nl_last) v |= 10ull << (8 * nb);
+    sk.ent(P.ne, v | fw_meta(n, 1));
+    sk.desc(P.np, fr_desc(1, P.ne));
+    big(1, n, P.np, true);
+    P.ne++; P.np++; P.maxl += n;
+  }
+  A5X_HD void close_group(bool c, bool tail) {
+    if (c) sk.gst(0, P.ng & 7u, gd | ((u64)tail << 17));
+    big(cR, cmax, (u32)(gd >> 39) & 127u, c);
+    P.ne += c ? cR : 0u; P.ng += c ? 1u : 0u; P.maxl += c ? cmax : 0u;
+    cR = c ? 0u : cR;
+  }
+  A5X_HD void unit(const Unit& U) {
+    if (!P.ok) return;
+    const u32 Ru = U.R, ml = U.ml, run = U.s - prev;
+    if (!U.ok || ml > FW_PLEN || Ru > CAP || Ru < 2) { P.ok = false; return; }
+    const bool open = cR != 0, merge = open && cmax + run + ml <= FW_PLEN && cR * Ru <= CAP;
+    close_group(open && !merge, false);
+    u32 off = prev, rem = run;
+    while (!merge && rem + ml > FW_PLEN) {  // literal run that does not fit with the unit
+      const u32 n = umin32(FW_PLEN, rem);
+      literal(off, n, false);
+      off += n; rem -= n;
+    }
+    const u32 nm = (u32)(gd >> 15) & 3u;  // members of the open group
+    const u64 fresh = (u64)(off & 127u) | ((u64)(nu & 255u) << 7) | (1ull << 15) | ((u64)(P.ne & 1023u) << 18) |
+                      ((u64)(Ru - 1u) << 30) | ((u64)(P.np & 127u) << 39);
+    gd = merge ? (gd + (1ull << 15)) | ((u64)(Ru - 1u) << (30u + 3u * nm)) : fresh;
+    cR = merge ? cR * Ru : Ru;
+    cmax = merge ? cmax + run + ml : rem + ml;
+    P.np += merge ? 0u : 1u;
+    prev = U.e;
+    nu++;
+  }
+  A5X_HD void finish(u32 L) {  // tail bytes + '\n'
+    if (!P.ok) return;
+    const u32 tl = L - prev + 1;
+    const bool open = cR != 0, tm = open && cmax + tl <= FW_PLEN;
+    cmax += tm ? tl : 0u;
+    close_group(open, tm);
+    u32 off = prev, rem = tm ? 0u : tl;
+    while (rem) {
+      const u32 n = umin32(FW_PLEN, rem);
+      literal(off, n, n == rem);
+      off += n; rem -= n;
+    }
+  }
+  // Entries and piece descriptor of group g (< P.ng, < 8).  Entry a = the lead run, then for
+  // each member in order its choice d_j and the bytes after it (the run to the next member;
+  // after the last one the tail and '\n' when they joined), d_j the mixed-radix digits of a
+  // over the members' R, first member least significant (Planner's a1 + cR * a2).  A group
+  // is <= FW_PLEN bytes in every entry, so no shift below reaches 64 bits.
+  A5X_HD void build_group(u32 g, u32 L) {
+    const u64 d = sk.gld(0, g & 7u);
+    const u32 off = (u32)d & 127u, i0 = (u32)(d >> 7) & 255u, nm = (u32)(d >> 15) & 3u;
+    const u32 ebase = (u32)(d >> 18) & 1023u, pi = (u32)(d >> 39) & 127u;
+    const bool tail = (d >> 17) & 1u;
+    u32 R[3], cb[3], pl[3];
+    u64 pv[3];
+    u32 at = off, ll = 0;  // the byte after the last member; the lead run's length
+    u64 lv = 0;
+    // the group's source bytes, read once: runs and keys are <= FW_PLEN bytes together (a key
+    // is no longer than its unit's longest choice, which the piece limit counts)
+    const u64 src = wd.ld(off, umin32(FW_PLEN, L - off));
+#pragma unroll
+    for (u32 j = 0; j < 3; j++) {
+      R[j] = ((u32)(d >> (30u + 3u * j)) & 7u) + 1u;
+      cb[j] = 0; pl[j] = 0; pv[j] = 0;
+      if (j < nm) {
+        const u32 e = ul(i0 + j), q = e >> 10;
+        const A5xKey& key = T.keys[e & 1023u];
+        cb[j] = key.choice_base;
+        const u32 n = q - at;  // the run before the member: the lead, or after member j - 1
+        const u64 v = keep_bytes64(src >> (8 * (at - off)), n);
+        if (j == 0) { lv = v; ll = n; }
+        if (j == 1) { pv[0] = v; pl[0] = n; }
+        if (j == 2) { pv[1] = v; pl[1] = n; }
+        at = q + key.klen;
+      }
+    }
+    if (tail) {
+      const u32 n = L - at;
+      const u64 v = keep_bytes64(src >> (8 * (at - off)), n) | (10ull << (8 * n));
+#pragma unroll
+      for (u32 j = 0; j < 3; j++)
+        if (j + 1 == nm) { pv[j] = v; pl[j] = n + 1u; }
+    }
+    // Entry a = d0 + R0 (d1 + R1 d2): the bytes after member 0's choice depend on (d1, d2)
+    // alone, so they are put together once per (d1, d2) (<= 4: R0 >= 2) and each of the R0
+    // entries that share them costs one choice read and two appends.
+    const u32 cRg = R[0] * R[1] * R[2], nsuf = R[1] * R[2];
+    u32 d1 = 0, d2 = 0;
+    for (u32 s = 0; s < nsuf; s++) {
+      u64 sv = pv[0];
+      u32 sn = pl[0];
+      if (nm > 1) {
+        const u64 c = T.cval[cb[1] + d1];
+        sv |= (c & FW_M56) << (8 * sn);
+        sn += (u32)(c >> 56);
+        sv |= pv[1] << (8 * sn);
+        sn += pl[1];
+      }
+      if (nm > 2) {
+        const u64 c = T.cval[cb[2] + d2];
+        sv |= (c & FW_M56) << (8 * sn);
+        sn += (u32)(c >> 56);
+        sv |= pv[2] << (8 * sn);
+        sn += pl[2];
+      }
+      const u32 eb = ebase + R[0] * s;
+      for (u32 a = 0; a < R[0]; a++) {  // (a plain loop: unrolled 8 times with guards it measured 20 us slower)
+        const u64 c = T.cval[cb[0] + a];
+        const u32 n = ll + (u32)(c >> 56);
+        const u64 v = lv | ((c & FW_M56) << (8 * ll)) | (sv << (8 * n));
+        sk.ent(eb + a, (v & FW_M56) | fw_meta(n + sn, cRg));
+      }
+      d1++;
+      const bool w1 = d1 == R[1];
+      d1 = w1 ? 0u : d1; d2 += w1 ? 1u : 0u;
+    }
+    sk.desc(pi, (u64)fr_magic8(cRg) | ((u64)(ebase & 255u) << 32) | ((u64)(cRg - 1u) << 40));
+  }
+};
+
 template <bool BUILD, class W, class S>
 A5X_HD Plan plan_word(const W& wd, u32 L, const Tab& T, S& sk, u32 balanced_cap = 0) {
   Planner<BUILD, W, S> pl(wd, T, sk, balanced_cap);
@@ -774,6 +954,10 @@ A5X_HD Plan plan_word_cached(const W& wd, u32 L, const Tab& T, S& sk, const Unit
 #define FB_BAL_SLACK8 0  // off: measured on C3 (A/B, one box) the balanced grouping left the
                          // expansion at 8.78-8.80 ms and cost the keyspace 0.54 ms (3.14 -> 3.68)
 #endif
+// PieceBuilder (k_keyspace_thread's replayed words) keeps the greedy grouping only, while the
+// fused walk, k_keyspace_cplx and the host replay call pick_balanced(): a build with the
+// balanced grouping on would give the same word other big pieces by the path it takes.
+static_assert(FB_BAL_SLACK8 == 0, "PieceBuilder does not track the balanced big-piece grouping");
 A5X_HD u32 fb_balanced_cap(u64 P, u32 slack8 = FB_BAL_SLACK8) {
   if (!slack8 || P <= FB_RMAX) return 0;
   u32 nb = 1;
@@ -875,6 +1059,82 @@ A5X_HD WordClass classify_finish(const CountAcc& A, const Plan& PL, u32 L, int m
     C.flags = A.clusters ? 0u : (A5X_WF_RADIX | (A.bin ? A5X_WF_BIN : 0u));
   }
   return C;
+}
+
+// Host check of PieceBuilder against Planner<true, ., ., 8> on one word (a5x_debug_piece_build,
+// tools/piece_build_selftest.cpp): wd = the word's L <= 127 bytes; nothing past them is read
+// (GWord::at / ld take the bytes they are asked for, and both planners ask inside the word: the
+// self-test passes exact-size blocks under AddressSanitizer).  out[0] = PB_EQUAL / PB_DIFFERENT / PB_NA (a cluster, a key index >= 1024, or a unit
+// the 8-entry group refuses: then both planners must refuse, else PB_DIFFERENT) / PB_NOTFAST
+// (not FAST and more than 8 groups: the kernel never builds it and the group list does not
+// hold it; any other word is compared, FAST or not); out[1..8] = units, np, ng, ne, most
+// members in a group, groups the tail joined, literal pieces (of the builder's plan; the
+// tests' coverage counters), the word is FAST.
+enum { PB_EQUAL = 0, PB_DIFFERENT = 1, PB_NA = 2, PB_NOTFAST = 3 };
+struct ULogArr {
+  const u32* p;
+  A5X_HD u32 operator()(u32 i) const { return p[i]; }
+};
+inline void piece_build_compare(const uint8_t* wd, u32 L, const Tab& T, uint32_t* out) {
+  constexpr u32 NREC = 1 + 128 + 128 * 8 + 128 + 16;  // (np <= 128, ne <= 8 per byte, of any word of <= 127 bytes)
+  static_assert(NREC >= 1 + 128 + 1023 + 8, "the builder's masked entry indices stay inside");
+  for (int j = 0; j < 9; j++) out[j] = 0;
+  GWord gw;
+  gw.p = wd;
+  u32 log[128], nu = 0, p = 0;
+  bool na = false;
+  CountAcc A;
+  count_init(A, L);
+  CountPlanner<8> cp;
+  Unit U;
+  while (next_unit(gw, L, p, T, U)) {
+    if (U.k || !U.ok || U.key >= 1024u || nu >= 128u) { na = true; break; }
+    log[nu++] = (U.s << 10) | U.key;
+    count_unit(A, U);
+    cp.unit(U);
+  }
+  out[0] = PB_NA; out[1] = nu;
+  if (na) return;
+  cp.finish(L);
+  u64 ra[NREC], rb[NREC];
+  for (u32 i = 0; i < NREC; i++) ra[i] = rb[i] = 0;
+  ArraySink sa, sb;
+  sa.rec = ra; sa.np = cp.P.ok ? cp.P.np : 128u;
+  sb.rec = rb; sb.np = sa.np;
+  for (u32 i = 0; i < FW_UMAXR; i++) sa.g[i] = sa.c[i] = sb.g[i] = sb.c[i] = 0;
+  Planner<true, GWord, ArraySink, 8> pa(gw, T, sa);
+  ULogArr lg;
+  lg.p = log;
+  PieceBuilder<GWord, ArraySink, ULogArr, 8> pb(gw, T, sb, lg);
+  for (u32 i = 0; i < nu; i++) {
+    lone_unit(T, log[i] >> 10, log[i] & 1023u, U);
+    pa.unit(U);
+    pb.unit(U);
+  }
+  pa.finish(L);
+  pb.finish(L);
+  if (!pa.P.ok || !pb.P.ok) {
+    out[0] = !pa.P.ok && !pb.P.ok && !cp.P.ok ? PB_NA : PB_DIFFERENT;
+    return;
+  }
+  out[2] = pb.P.np; out[3] = pb.P.ng; out[4] = pb.P.ne; out[7] = pb.P.np - pb.P.ng;
+  const WordClass C = classify_finish(A, cp.P, L, 0, 1 << 30, A5X_RING_A - 16);
+  out[8] = (C.flags & A5X_WF_FAST) && !(C.flags & A5X_WF_DEFER) ? 1u : 0u;
+  if (pb.P.ng > 8u) {
+    out[0] = out[8] ? PB_DIFFERENT : PB_NOTFAST;  // (a FAST word has <= FW_PMAX pieces)
+    return;
+  }
+  for (u32 g = 0; g < pb.P.ng; g++) {
+    const u64 d = sb.gld(0, g);
+    out[5] = umax32(out[5], (u32)(d >> 15) & 3u);
+    out[6] += (u32)(d >> 17) & 1u;
+    pb.build_group(g, L);
+  }
+  ra[0] = fr_hdr(pa.P.np, pa.P.ng, pa.P.ne, pa.P.maxl, pa.P.nbig, pa.P.bstarts, pa.P.bRp);
+  rb[0] = fr_hdr(pb.P.np, pb.P.ng, pb.P.ne, pb.P.maxl, pb.P.nbig, pb.P.bstarts, pb.P.bRp);
+  bool eq = pa.P.bent == pb.P.bent && pa.P.np == cp.P.np && pa.P.ne == cp.P.ne && pa.P.ng == cp.P.ng;
+  for (u32 i = 0; i < NREC; i++) eq = eq && ra[i] == rb[i];
+  out[0] = eq ? PB_EQUAL : PB_DIFFERENT;
 }
 
 // One walk over the units: counts and the piece plan (count mode) together.  uc: the

@@ -393,6 +393,17 @@ A5X_API int a5x_debug_plan_word(a5x_ctx* ctx, const uint8_t* word, size_t len, i
  * not fit the unit cache, 3 not a FAST word (no record); out[33..39] = 0. */
 A5X_API int a5x_debug_plan_sizes(a5x_ctx* ctx, const uint8_t* word, size_t len, uint32_t* out);
 
+/* Test hook (CPU test suite): the record of ONE word (<= 127 bytes) of lone matches as the
+ * build pass of k_keyspace_thread writes it (decisions per unit, a group's entries once per
+ * piece) against the build-mode planner with groups of <= 8 entries.  out[9]: out[0] = 0 the
+ * two records are equal (header, piece descriptors, entries), 1 different, 2 not applicable
+ * (overlapping matches, a key index >= 1024, or a unit that an 8-entry group does not take
+ * and both planners refuse), 3 not a FAST word and not comparable (more than 8 group
+ * pieces; every other word is compared, FAST or not); out[1..8] = units, pieces, group
+ * pieces, entries, most units in one group, groups that hold the tail, literal pieces, 1
+ * when the word is FAST. */
+A5X_API int a5x_debug_piece_build(a5x_ctx* ctx, const uint8_t* word, size_t len, uint32_t* out);
+
 /* Test hook (GPU test suite): how many words of the context's last keyspace pass (any
  * a5x_keyspace* / a5x_expand* call, every mode) k_keyspace_thread could not hold in its
  * per-word unit log (more than 16 lone matches, a match at byte >= 64, a key index
