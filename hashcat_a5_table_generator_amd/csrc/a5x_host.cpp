@@ -72,6 +72,52 @@ struct DevBuf {
   size_t cap = 0;  // elements
 };
 
+// The device scalar block a5x_ctx::d_scalars, in u32 words; h_scalars is its pinned host image
+// (read_scalars).  The keyspace passes clear all of it, [0, S_COUNT).
+enum Slot : uint32_t {
+  S_DEFER_N = 0,     // default keyspace: words k_keyspace_thread defers to the wave kernel
+  S_NBIG = 1,        // default keyspace: BIG words (big_list)
+  S_ERR = 2,         // the error word of every kernel (decode_dev_err)
+  S_NSLOW = 3,       // default keyspace: slow words (slow_list)
+  S_CPLX_N = 4,      // default keyspace: complex words (cplx), against the record slots offered
+  S_SLOW_SEGS = 5,   // job_launch: the range's slow segment items
+  S_BIG_SEGS = 6,    //   and its BIG ones (the two are cleared together)
+  S_GLOB_N = 7,      // both engines: pass G words (glob)
+  // Two uses that never overlap in time: k_hibytes sets the flag and k_keyspace_thread reads it
+  // inside one a5x_launch_keyspace, and nothing reads it afterwards; every digest route clears
+  // the word before each of its launches (hits_run), behind the keyspace on the same stream.
+  S_HIFLAG = 8,      // keyspace: the batch has bytes >= 0x80
+  S_NHITS = 8,       // digest routes: hits found by one launch, beyond the hit buffer's room too
+  // Again two: the virtual-word split runs in the -s / -s -r keyspace only, the hybrid gathers
+  // its sub-batch in default mode only, after the keyspace, and clears the word first.
+  S_VLONG_N = 9,     // -s / -s -r keyspace: words k_keyspace_vsub leaves to its large stage (m_cl2)
+  S_NONFAST_N = 9,   // fused default route: candidate-bearing words the fused kernel skipped (hy_list)
+  S_VREC_N = 10,     // -s / -s -r keyspace: sub-word record u64 needed, one u64 in [10, 11]
+  S_PROBE_N = 12,    // -r / -s keyspace: words the FAST probe leaves to the mode engine (m_cl);
+                     //   without the probe, k_mode_count_thread's left-over list
+  S_MCT_N = 13,      // -s / -s -r keyspace: k_mode_count_thread's left-over list behind the probe (m_cl2)
+  S_ROV_N = 14,      // -r / -s keyspace: words a tile could not decide, against the overflow slots offered
+  S_VOUT_N = 15,     // -s / -s -r keyspace: words the split leaves to the mode engine (m_vl)
+  S_GUARD = 16,      // the bounds guard's record, 8 u64 in [16, 31] (decode_dev_err)
+  S_REFIT = 32,      // keyspace words walked twice (a5x_debug_keyspace_refit)
+  S_TSPAN = 33,      // largest tile span of the batch (k_tile_span)
+  S_STAGE = 34,      // word stage the keyspace pass used (a5x_debug_keyspace_stage)
+  S_COUNT = 35,      // device words in use
+  H_RANGE_ERR = 36,  // host image only: a5x_expand_range's error word per output buffer, [36, 37]
+  S_ALLOC = 64       // words allocated, device and host
+};
+static_assert(S_COUNT <= H_RANGE_ERR && H_RANGE_ERR + 2 <= S_ALLOC, "the scalar block holds every slot");
+
+// a5x_ctx::h_totals (pinned u64): the scan totals read back
+enum Total : uint32_t {
+  T_CANDS = 0,   // the batch's candidates
+  T_BYTES = 1,   // its output bytes; -r / -s keyspace: its mode items, then its bytes
+  T_LINES = 2,   // stream_count_lines: the stream's lines
+  T_VWORDS = 3,  // build_virtual: sub-words added to the word list
+  T_VREC = 4,    //   and their record u64
+  T_ALLOC = 8
+};
+
 }  // namespace
 
 struct a5x_ctx {
@@ -167,9 +213,9 @@ struct a5x_ctx {
   uint8_t* gscr = nullptr;  // pass G scratch: A5X_G_SLOTS x a5x_gslot_bytes(), allocated on first use
   DevBuf<uint64_t> rec;  // FAST plan records (keyspace tiles of FW_TILE_REC u64)
   bool ks_large_only = false;  // a5x_debug_keyspace_large_stage: the small word stage is not offered
-  uint32_t* d_scalars = nullptr;  // [0] defer_n, [1] nbig, [2] err, [3] nslow, [4] cplx_n, [5] slow segs, [6] BIG segs, [16..31] guard record, [32] keyspace words walked twice (a5x_debug_keyspace_refit), [33] largest tile span of the batch (k_tile_span), [34] word stage the keyspace pass used (a5x_debug_keyspace_stage)
-  uint32_t* h_scalars = nullptr;  // pinned
-  uint64_t* h_totals = nullptr;   // pinned [0] cands [1] bytes [2..3] locate
+  uint32_t* d_scalars = nullptr;  // S_ALLOC words, indexed by Slot
+  uint32_t* h_scalars = nullptr;  // pinned, its host image
+  uint64_t* h_totals = nullptr;   // pinned, T_ALLOC u64 indexed by Total
 
   // host-API staging: words, and the double-buffered output stream of a5x_expand
   // (two HBM range buffers, two pinned host buffers, a copy stream; main.go:58-68)
@@ -235,6 +281,12 @@ void release(DevBuf<T>& b) {
   if (b.p) (void)hipFree(b.p);
   b.p = nullptr;
   b.cap = 0;
+}
+
+// Device slots [0, last] into h_scalars, behind the stream's work: valid once the caller has
+// synchronised the stream.
+hipError_t read_scalars(a5x_ctx* c, hipStream_t st, Slot last) {
+  return hipMemcpyAsync(c->h_scalars, c->d_scalars, (last + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
 }
 
 // readSubstitutionTable on one file's bytes, merged into t (main.go:108-144 + 40-50)
@@ -460,7 +512,7 @@ int decode_dev_err(a5x_ctx* c, uint32_t e) {
   if (!e) return A5X_OK;
   if (e & 32u) {
     uint64_t d[8] = {0};
-    (void)hipMemcpy(d, c->d_scalars + 16, sizeof d, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(d, c->d_scalars + S_GUARD, sizeof d, hipMemcpyDeviceToHost);
     return fail(c, A5X_E_HIP,
                 "device bounds guard tripped: code %llu ctx {%llu, %llu, %llu, %llu} block %llu thread %llu",
                 (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2],
@@ -504,6 +556,41 @@ struct Batch {  // device-side per-batch state after keyspace
   const uint64_t* byte_off = nullptr;
 };
 
+// Exclusive scans of the per-word a and b (n entries) into pa and pb, their totals into
+// h_totals[T_CANDS] / [T_BYTES], device slots [0, last] into h_scalars; synchronises.
+int scan_totals(a5x_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* pa, uint64_t* pb, Slot last,
+                hipStream_t st) {
+  HIPCHK(c, a5x_launch_scan(a, b, n, pa, pb, c->scan_tmp.p, c->d_scalars + S_ERR, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_totals + T_CANDS, pa + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_totals + T_BYTES, pb + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, read_scalars(c, st, last));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return A5X_OK;
+}
+
+// Diagnostics of a keyspace error: the first offending word, appended to the error text
+// (with_flags: the default engine's text, which shows the word's flags too).
+void name_offending_word(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uint64_t nw, bool with_flags) {
+  std::vector<uint32_t> fl(nw);
+  std::vector<uint64_t> wo(nw + 1);
+  if (!nw || hipMemcpy(fl.data(), c->flags.p, nw * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(wo.data(), d_woff, (nw + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return;
+  for (uint64_t i = 0; i < nw; i++)
+    if (fl[i] & (A5X_WF_ERR_BIG | A5X_WF_ERR_OVF)) {
+      std::string w((size_t)(wo[i + 1] - wo[i]), '\0');
+      (void)hipMemcpy(&w[0], d_words + wo[i], w.size(), hipMemcpyDeviceToHost);
+      char tail[160];
+      if (with_flags)
+        snprintf(tail, sizeof tail, " [word %llu len %zu flags 0x%08x: %.40s]", (unsigned long long)i, w.size(),
+                 fl[i], w.c_str());
+      else
+        snprintf(tail, sizeof tail, " [word %llu len %zu: %.40s]", (unsigned long long)i, w.size(), w.c_str());
+      c->err += tail;
+      return;
+    }
+}
+
 // keyspace -> flags, per-word counts/bytes, exclusive scans (synchronises once)
 int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uint64_t nw, int mn, int mx,
                  uint64_t* d_cand_off, uint64_t* d_byte_off, hipStream_t st, Batch* B, bool timed) {
@@ -532,42 +619,40 @@ int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uin
     d_byte_off = c->byte_off.p;
   }
   if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 140, st));  // scalars + guard debug record + [32..34]
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, S_COUNT * sizeof(uint32_t), st));
   A5xKsLaunch K;
   memset(&K, 0, sizeof K);
   if (nw > 0) {
     K.table = c->d_table; K.table_bytes = c->table_bytes; K.words = d_words; K.woff = d_woff; K.nw = nw;
     K.mn = mn; K.mx = mx; K.count = c->count.p; K.bytes = c->bytes.p; K.flags = c->flags.p;
-    K.defer_list = c->defer.p; K.defer_n = c->d_scalars; K.nbig = c->d_scalars + 1; K.err = c->d_scalars + 2;
-    K.hiflag = table_lead_only(c) ? c->d_scalars + 8 : nullptr;
-    K.nrefit = c->d_scalars + 32;
+    K.defer_list = c->defer.p; K.defer_n = c->d_scalars + S_DEFER_N; K.nbig = c->d_scalars + S_NBIG;
+    K.err = c->d_scalars + S_ERR;
+    K.hiflag = table_lead_only(c) ? c->d_scalars + S_HIFLAG : nullptr;
+    K.nrefit = c->d_scalars + S_REFIT;
     K.small_stage = c->ks_large_only ? 0u : a5x_keyspace_small_stage(c->table_bytes);
-    K.tspan = c->d_scalars + 33; K.stage_used = c->d_scalars + 34;
-    K.nslow = c->d_scalars + 3;
+    K.tspan = c->d_scalars + S_TSPAN; K.stage_used = c->d_scalars + S_STAGE;
+    K.nslow = c->d_scalars + S_NSLOW;
     K.slow_list = c->slow_list.p; K.big_list = c->big_list.p;
     K.rec = c->rec.p; K.roff = c->roff.p;
-    K.cplx_list = c->cplx.p; K.cplx_n = c->d_scalars + 4; K.cplx_cap = (uint32_t)ccap;
+    K.cplx_list = c->cplx.p; K.cplx_n = c->d_scalars + S_CPLX_N; K.cplx_cap = (uint32_t)ccap;
     K.cplx_base = ((nw + FW_TILE - 1) / FW_TILE) * (uint64_t)FW_TILE_REC;
     K.defer_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nw, (uint64_t)c->cus * 4));
-    K.glob_list = c->glob.p; K.glob_n = c->d_scalars + 7;
+    K.glob_list = c->glob.p; K.glob_n = c->d_scalars + S_GLOB_N;
     HIPCHK(c, a5x_launch_keyspace(K, st));
-    HIPCHK(c, a5x_launch_scan(c->count.p, c->bytes.p, nw, d_cand_off, d_byte_off, c->scan_tmp.p,
-                              c->d_scalars + 2, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_totals, d_cand_off + nw, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_totals + 1, d_byte_off + nw, 8, hipMemcpyDeviceToHost, st));
+    if ((rc = scan_totals(c, c->count.p, c->bytes.p, nw, d_cand_off, d_byte_off, S_GLOB_N, st))) return rc;
   } else {
     HIPCHK(c, hipMemsetAsync(d_cand_off, 0, 8, st));
     HIPCHK(c, hipMemsetAsync(d_byte_off, 0, 8, st));
-    c->h_totals[0] = c->h_totals[1] = 0;
+    c->h_totals[T_CANDS] = c->h_totals[T_BYTES] = 0;
+    HIPCHK(c, read_scalars(c, st, S_GLOB_N));
+    HIPCHK(c, hipStreamSynchronize(st));
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (nw > 0 && c->h_scalars[4] > ccap) {
+  if (nw > 0 && c->h_scalars[S_CPLX_N] > ccap) {
     // more complex words than record slots: room for all of them, and the keyspace again
-    c->cplx_need = c->h_scalars[4];
+    c->cplx_need = c->h_scalars[S_CPLX_N];
     return run_keyspace(c, d_words, d_woff, nw, mn, mx, d_cand_off, d_byte_off, st, B, timed);
   }
-  if (nw > 0 && c->h_scalars[2] == 0 && c->h_scalars[7] > 0) {
+  if (nw > 0 && c->h_scalars[S_ERR] == 0 && c->h_scalars[S_GLOB_N] > 0) {
     // pass G: words beyond the pass-B LDS budget are sized in HBM scratch slots (their
     // counts were 0 in the first scan), then the scan runs again
     if (!c->gscr) {
@@ -577,37 +662,17 @@ int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uin
     }
     K.gscr = c->gscr; K.gslots = A5X_G_SLOTS;
     HIPCHK(c, a5x_launch_keyspace_g(K, st));
-    HIPCHK(c, a5x_launch_scan(c->count.p, c->bytes.p, nw, d_cand_off, d_byte_off, c->scan_tmp.p,
-                              c->d_scalars + 2, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_totals, d_cand_off + nw, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_totals + 1, d_byte_off + nw, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    if ((rc = scan_totals(c, c->count.p, c->bytes.p, nw, d_cand_off, d_byte_off, S_GLOB_N, st))) return rc;
   }
-  if ((rc = decode_dev_err(c, c->h_scalars[2]))) {
-    // name the first offending word (diagnostics)
-    std::vector<uint32_t> fl(nw);
-    std::vector<uint64_t> wo(nw + 1);
-    if (nw && hipMemcpy(fl.data(), c->flags.p, nw * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-        hipMemcpy(wo.data(), d_woff, (nw + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-      for (uint64_t i = 0; i < nw; i++)
-        if (fl[i] & (A5X_WF_ERR_BIG | A5X_WF_ERR_OVF)) {
-          std::string w((size_t)(wo[i + 1] - wo[i]), '\0');
-          (void)hipMemcpy(&w[0], d_words + wo[i], w.size(), hipMemcpyDeviceToHost);
-          char tail[160];
-          snprintf(tail, sizeof tail, " [word %llu len %zu flags 0x%08x: %.40s]", (unsigned long long)i, w.size(),
-                   fl[i], w.c_str());
-          c->err += tail;
-          break;
-        }
-    }
+  if ((rc = decode_dev_err(c, c->h_scalars[S_ERR]))) {
+    name_offending_word(c, d_words, d_woff, nw, true);
     return rc;
   }
-  B->total_cands = nw ? c->h_totals[0] : 0;
-  B->total_bytes = nw ? c->h_totals[1] : 0;
-  B->nbig = c->h_scalars[1];
-  B->nslow = c->h_scalars[3];
-  B->nglob = nw ? c->h_scalars[7] : 0;
+  B->total_cands = nw ? c->h_totals[T_CANDS] : 0;
+  B->total_bytes = nw ? c->h_totals[T_BYTES] : 0;
+  B->nbig = c->h_scalars[S_NBIG];
+  B->nslow = c->h_scalars[S_NSLOW];
+  B->nglob = nw ? c->h_scalars[S_GLOB_N] : 0;
   B->cand_off = d_cand_off;
   B->byte_off = d_byte_off;
   return A5X_OK;
@@ -619,8 +684,8 @@ A5xExpLaunch exp_launch(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_wo
   memset(&E, 0, sizeof E);
   E.table = c->d_table; E.table_bytes = c->table_bytes; E.words = d_words; E.woff = d_woff; E.nw = nw;
   E.cand_off = B.cand_off; E.byte_off = B.byte_off; E.flags = c->flags.p; E.chunk_w0 = c->chunk_w0.p;
-  E.CH = c->chunk; E.SEG = c->seg; E.mn = mn; E.mx = mx; E.err = c->d_scalars + 2;
-  E.dbg = (uint64_t*)(c->d_scalars + 16);
+  E.CH = c->chunk; E.SEG = c->seg; E.mn = mn; E.mx = mx; E.err = c->d_scalars + S_ERR;
+  E.dbg = (uint64_t*)(c->d_scalars + S_GUARD);
   E.waves_per_block = c->waves_per_block;
   E.waves_per_block_fast = c->waves_per_block_fast;
   E.rec = c->rec.p; E.roff = c->roff.p; E.rec_n = c->rec.cap;
@@ -734,8 +799,8 @@ A5xModeLaunch mode_launch(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_
   M.seg_off = c->m_seg_off.p; M.item_w = c->m_item_w.p; M.nitems = c->m_items;
   M.seg_bytes = c->m_seg_bytes.p; M.seg_boff = c->m_seg_boff.p; M.item_fl = c->m_item_fl.p;
   M.cand_begin = 0; M.cand_end = ~0ull;
-  M.err = c->d_scalars + 2;
-  M.glob_list = c->glob.p; M.glob_n = c->d_scalars + 7;
+  M.err = c->d_scalars + S_ERR;
+  M.glob_list = c->glob.p; M.glob_n = c->d_scalars + S_GLOB_N;
   if (c->m_nglob) { M.gscr = c->mgscr; M.gslots = A5X_G_SLOTS; }
   return M;
 }
@@ -749,11 +814,11 @@ int build_virtual(a5x_ctx* c, uint64_t nw, const uint8_t* d_words, const uint64_
   int rc;
   if ((rc = grow(c, c->vpre, nw + 1)) || (rc = grow(c, c->vrpre, nw + 1))) return rc;
   HIPCHK(c, a5x_launch_vwords_sizes(c->flags.p, d_cand_off, nw, c->vn.p, c->vrsz.p, st));
-  HIPCHK(c, a5x_launch_scan(c->vn.p, c->vrsz.p, nw, c->vpre.p, c->vrpre.p, c->scan_tmp.p, c->d_scalars + 2, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_totals + 4, c->vpre.p + nw, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_totals + 5, c->vrpre.p + nw, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, a5x_launch_scan(c->vn.p, c->vrsz.p, nw, c->vpre.p, c->vrpre.p, c->scan_tmp.p, c->d_scalars + S_ERR, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_totals + T_VWORDS, c->vpre.p + nw, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_totals + T_VREC, c->vrpre.p + nw, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
-  const uint64_t nv = nw + c->h_totals[4], nrec = c->h_totals[5];
+  const uint64_t nv = nw + c->h_totals[T_VWORDS], nrec = c->h_totals[T_VREC];
   if (nv > 0xffffffffull || nrec + 4 > 0xffffffffull)
     return fail(c, A5X_E_ARG, "batch of %llu words is too large for one -s call (virtual word list)",
                 (unsigned long long)nw);
@@ -823,7 +888,7 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
     d_byte_off = c->byte_off.p;
   }
   if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 140, st));  // (with [32..34])
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, S_COUNT * sizeof(uint32_t), st));
   B->cand_off = d_cand_off;
   B->byte_off = d_byte_off;
   B->nbig = B->nslow = 0;
@@ -879,23 +944,23 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
     memset(&K, 0, sizeof K);
     K.table = c->d_table; K.table_bytes = c->table_bytes; K.words = d_words; K.woff = d_woff; K.nw = nw;
     K.mn = mn; K.mx = mx; K.count = c->count.p; K.bytes = c->bytes.p; K.flags = c->flags.p;
-    K.err = c->d_scalars + 2; K.rec = c->rec.p; K.roff = c->roff.p;
+    K.err = c->d_scalars + S_ERR; K.rec = c->rec.p; K.roff = c->roff.p;
     K.rmode = mode; K.rcmin = mn > 0 ? 1u : 0u; K.rnseg = c->m_nseg.p; K.rseg = c->mseg;
-    K.defer_list = c->m_cl.p; K.defer_n = c->d_scalars + 12;
-    K.cplx_list = c->cplx.p; K.cplx_n = c->d_scalars + 14; K.cplx_cap = (uint32_t)rcap; K.cplx_base = rtiles;
+    K.defer_list = c->m_cl.p; K.defer_n = c->d_scalars + S_PROBE_N;
+    K.cplx_list = c->cplx.p; K.cplx_n = c->d_scalars + S_ROV_N; K.cplx_cap = (uint32_t)rcap; K.cplx_base = rtiles;
     K.defer_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + 255) / 256, (uint64_t)c->cus * 2));
     K.vocc = vsub ? c->vocc.p : nullptr;
-    K.hiflag = table_lead_only(c) ? c->d_scalars + 8 : nullptr;
-    K.nrefit = c->d_scalars + 32;
+    K.hiflag = table_lead_only(c) ? c->d_scalars + S_HIFLAG : nullptr;
+    K.nrefit = c->d_scalars + S_REFIT;
     K.small_stage = c->ks_large_only ? 0u : a5x_keyspace_small_stage(c->table_bytes);
-    K.tspan = c->d_scalars + 33; K.stage_used = c->d_scalars + 34;
+    K.tspan = c->d_scalars + S_TSPAN; K.stage_used = c->d_scalars + S_STAGE;
     HIPCHK(c, a5x_launch_keyspace(K, st));
     if (vsub) {
-      K.vout_list = c->m_vl.p; K.vout_n = c->d_scalars + 15;
+      K.vout_list = c->m_vl.p; K.vout_n = c->d_scalars + S_VOUT_N;
       K.vn = c->vn.p; K.vrsz = c->vrsz.p; K.vrec = c->vrec.p;
-      K.vrec_n = (uint64_t*)(c->d_scalars + 10); K.vrec_cap = vcap;
+      K.vrec_n = (uint64_t*)(c->d_scalars + S_VREC_N); K.vrec_cap = vcap;
       if (!getenv("A5X_VSUB_LARGE_ONLY")) {  // (m_cl2 is free until k_mode_count_thread below)
-        K.vlong_list = c->m_cl2.p; K.vlong_n = c->d_scalars + 9;
+        K.vlong_list = c->m_cl2.p; K.vlong_n = c->d_scalars + S_VLONG_N;
       }
       HIPCHK(c, a5x_launch_vsub(K, st));
     }
@@ -903,29 +968,24 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
   A5xModeLaunch M = mode_launch(c, d_words, d_woff, nw, mode, mn, mx, rfast);
   if (mct) {
     M.in_list = vsub ? c->m_vl.p : rfast ? c->m_cl.p : nullptr;
-    M.in_n = vsub ? c->d_scalars + 15 : rfast ? c->d_scalars + 12 : nullptr;
+    M.in_n = vsub ? c->d_scalars + S_VOUT_N : rfast ? c->d_scalars + S_PROBE_N : nullptr;
     M.cl_list = rfast ? c->m_cl2.p : c->m_cl.p;
-    M.cl_n = c->d_scalars + (rfast ? 13 : 12);
+    M.cl_n = c->d_scalars + (rfast ? S_MCT_N : S_PROBE_N);
     HIPCHK(c, a5x_launch_mode_count_thread(M, st));
   } else if (rfast) {  // k_mode_count only over the words the probe left to the mode engine
     M.cl_list = c->m_cl.p;
-    M.cl_n = c->d_scalars + 12;
+    M.cl_n = c->d_scalars + S_PROBE_N;
   }
   HIPCHK(c, a5x_launch_mode_count(M, st));
-  HIPCHK(c, a5x_launch_scan(c->count.p, c->m_nseg.p, nw, d_cand_off, c->m_seg_off.p, c->scan_tmp.p,
-                            c->d_scalars + 2, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_totals, d_cand_off + nw, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_totals + 1, c->m_seg_off.p + nw, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (rfast && c->h_scalars[14] > rcap) {
+  if ((rc = scan_totals(c, c->count.p, c->m_nseg.p, nw, d_cand_off, c->m_seg_off.p, S_VOUT_N, st))) return rc;
+  if (rfast && c->h_scalars[S_ROV_N] > rcap) {
     // more undecided words than overflow slots: grow to fit them all and run again (the
     // undecided tail was left uncounted, so nothing of this pass is used)
-    c->rov_need = c->h_scalars[14];
+    c->rov_need = c->h_scalars[S_ROV_N];
     return run_keyspace_mode(c, d_words, d_woff, nw, mode, mn, mx, d_cand_off, d_byte_off, st, B, timed, lengths);
   }
   uint64_t vused = 0;
-  if (vsub) memcpy(&vused, c->h_scalars + 10, 8);
+  if (vsub) memcpy(&vused, c->h_scalars + S_VREC_N, 8);
   if (vsub && vused > vcap) {
     // more sub-word records than room: grow to fit them all and run again (words past
     // the room were left undecided)
@@ -935,11 +995,11 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
     c->vrec_need = vused;
     return run_keyspace_mode(c, d_words, d_woff, nw, mode, mn, mx, d_cand_off, d_byte_off, st, B, timed, lengths);
   }
-  B->nmode = vsub ? c->h_scalars[15] : rfast ? c->h_scalars[12] : nw;
+  B->nmode = vsub ? c->h_scalars[S_VOUT_N] : rfast ? c->h_scalars[S_PROBE_N] : nw;
   if (vsub && getenv("A5X_VSUB_DEBUG")) {  // (diagnostics: what the split leaves to the mode engine)
     fprintf(stderr, "[vsub] words %llu probe-left %u split-left %u vrec %llu\n", (unsigned long long)nw,
-            c->h_scalars[12], c->h_scalars[15], (unsigned long long)vused);
-    const uint32_t k = std::min<uint32_t>(c->h_scalars[15], 24);
+            c->h_scalars[S_PROBE_N], c->h_scalars[S_VOUT_N], (unsigned long long)vused);
+    const uint32_t k = std::min<uint32_t>(c->h_scalars[S_VOUT_N], 24);
     std::vector<uint32_t> li(k);
     std::vector<uint64_t> wo(nw + 1);
     if (k && hipMemcpy(li.data(), c->m_vl.p, 4 * k, hipMemcpyDeviceToHost) == hipSuccess &&
@@ -950,44 +1010,23 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
         fprintf(stderr, "[vsub]   left: %s\n", s.c_str());
       }
   }
-  if (c->h_scalars[2] == 0 && c->h_scalars[7] > 0) {
+  if (c->h_scalars[S_ERR] == 0 && c->h_scalars[S_GLOB_N] > 0) {
     // mode pass G: words longer than the LDS engines take are counted in HBM scratch
     // slots (their counts were 0 in the first scan), then the scan runs again
     if (!c->mgscr) {
       HIPCHK(c, hipMalloc((void**)&c->mgscr, (size_t)A5X_G_SLOTS * a5x_mode_gslot_bytes()));
     }
-    c->m_nglob = c->h_scalars[7];
+    c->m_nglob = c->h_scalars[S_GLOB_N];
     M = mode_launch(c, d_words, d_woff, nw, mode, mn, mx, rfast);
     HIPCHK(c, a5x_launch_mode_count_g(M, st));
-    HIPCHK(c, a5x_launch_scan(c->count.p, c->m_nseg.p, nw, d_cand_off, c->m_seg_off.p, c->scan_tmp.p,
-                              c->d_scalars + 2, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_totals, d_cand_off + nw, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_totals + 1, c->m_seg_off.p + nw, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    if ((rc = scan_totals(c, c->count.p, c->m_nseg.p, nw, d_cand_off, c->m_seg_off.p, S_GLOB_N, st))) return rc;
   }
-  auto name_word = [&]() {
-    std::vector<uint32_t> fl(nw);
-    std::vector<uint64_t> wo(nw + 1);
-    if (hipMemcpy(fl.data(), c->flags.p, nw * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-        hipMemcpy(wo.data(), d_woff, (nw + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-      for (uint64_t i = 0; i < nw; i++)
-        if (fl[i] & (A5X_WF_ERR_BIG | A5X_WF_ERR_OVF)) {
-          std::string w((size_t)(wo[i + 1] - wo[i]), '\0');
-          (void)hipMemcpy(&w[0], d_words + wo[i], w.size(), hipMemcpyDeviceToHost);
-          char tail[160];
-          snprintf(tail, sizeof tail, " [word %llu len %zu: %.40s]", (unsigned long long)i, w.size(), w.c_str());
-          c->err += tail;
-          break;
-        }
-    }
-  };
-  if ((rc = decode_dev_err(c, c->h_scalars[2]))) {
-    name_word();
+  if ((rc = decode_dev_err(c, c->h_scalars[S_ERR]))) {
+    name_offending_word(c, d_words, d_woff, nw, false);
     return rc;
   }
-  B->total_cands = c->h_totals[0];
-  const uint64_t items = c->h_totals[1];
+  B->total_cands = c->h_totals[T_CANDS];
+  const uint64_t items = c->h_totals[T_BYTES];
   c->m_items = items;
   if ((rc = grow(c, c->m_item_w, items + 1)) || (rc = grow(c, c->m_seg_bytes, items + 1)) ||
       (rc = grow(c, c->m_item_fl, items + 1)) ||
@@ -1005,24 +1044,24 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
   }
   if (items) HIPCHK(c, a5x_launch_plan(c->m_seg_off.p, nw, 1, c->m_item_w.p, st));
   if (!lengths) {
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, read_scalars(c, st, S_ERR));
     HIPCHK(c, hipStreamSynchronize(st));
-    if ((rc = decode_dev_err(c, c->h_scalars[2]))) return rc;
+    if ((rc = decode_dev_err(c, c->h_scalars[S_ERR]))) return rc;
     B->total_bytes = 0;
     return vused ? build_virtual(c, nw, d_words, d_woff, mode, mn, d_cand_off, nullptr, st, B) : A5X_OK;
   }
   if (items) HIPCHK(c, a5x_launch_mode_items(M, 0, st));
   if (items)
     HIPCHK(c, a5x_launch_scan(c->m_seg_bytes.p, c->m_seg_bytes.p, items, c->m_seg_boff.p, c->m_tmp.p,
-                              c->scan_tmp.p, c->d_scalars + 2, st));
+                              c->scan_tmp.p, c->d_scalars + S_ERR, st));
   else
     HIPCHK(c, hipMemsetAsync(c->m_seg_boff.p, 0, 8, st));
   HIPCHK(c, a5x_launch_mode_wordbytes(c->m_seg_off.p, c->m_seg_boff.p, nw, d_byte_off, c->bytes.p, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_totals + 1, d_byte_off + nw, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(c->h_totals + T_BYTES, d_byte_off + nw, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, read_scalars(c, st, S_ERR));
   HIPCHK(c, hipStreamSynchronize(st));
-  if ((rc = decode_dev_err(c, c->h_scalars[2]))) return rc;
-  B->total_bytes = c->h_totals[1];
+  if ((rc = decode_dev_err(c, c->h_scalars[S_ERR]))) return rc;
+  B->total_bytes = c->h_totals[T_BYTES];
   return vused ? build_virtual(c, nw, d_words, d_woff, mode, mn, d_cand_off, d_byte_off, st, B) : A5X_OK;
 }
 
@@ -1030,7 +1069,7 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
 // Batch jobs: the keyspace runs once per batch (job_prepare), then any number of
 // candidate ranges are located and expanded against it (job_locate, job_launch).
 // ---------------------------------------------------------------------------
-struct Job {
+struct Job {  // (opened as Job J{words, offsets, nw, mode, mn, mx, stream})
   const uint8_t* w = nullptr;
   const uint64_t* wo = nullptr;
   uint64_t nw = 0;
@@ -1060,9 +1099,9 @@ int job_prepare(a5x_ctx* c, Job& J, uint64_t* d_cand_off, uint64_t* d_byte_off, 
 }
 
 int job_check(a5x_ctx* c, const Job& J) {
-  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, J.st));
+  HIPCHK(c, read_scalars(c, J.st, S_ERR));
   HIPCHK(c, hipStreamSynchronize(J.st));
-  return decode_dev_err(c, c->h_scalars[2]);
+  return decode_dev_err(c, c->h_scalars[S_ERR]);
 }
 
 // Output byte (and -r/-s item) positions of global candidate indices q[0..n) (sorted or
@@ -1097,14 +1136,9 @@ int job_locate(a5x_ctx* c, const Job& J, const std::vector<uint64_t>& q, std::ve
   return A5X_OK;
 }
 
-Range range_of(const Job& J, uint64_t cb, uint64_t ce, const uint64_t* lb, const uint64_t* le) {
-  Range R;
-  R.cb = cb; R.ce = ce;
-  R.b0 = lb[0]; R.b1 = le[0];
-  R.i0 = lb[1];
-  R.i1 = le[1] + (le[2] ? 1 : 0);
-  (void)J;
-  return R;
+// the range [cb, ce) from job_locate's answers for cb (lb) and ce (le)
+Range range_of(uint64_t cb, uint64_t ce, const uint64_t* lb, const uint64_t* le) {
+  return Range{cb, ce, lb[0], le[0], lb[1], le[1] + (le[2] ? 1 : 0)};
 }
 
 // Cut [0, total) into ranges of at most cap output bytes: candidate boundaries spaced for
@@ -1125,7 +1159,7 @@ int plan_ranges(a5x_ctx* c, const Job& J, uint64_t cap, std::vector<Range>& out,
   }
   if (RB <= cap) {
     if (cb == 0 && ce == T) out.push_back(Range{0, T, 0, TB, 0, J.mode != A5X_MODE_DEFAULT ? c->m_items : 0});
-    else out.push_back(range_of(J, cb, ce, &ends[0], &ends[3]));
+    else out.push_back(range_of(cb, ce, &ends[0], &ends[3]));
     return A5X_OK;
   }
   const uint64_t K = std::max<uint64_t>(2, (RB + cap * 3 / 4 - 1) / std::max<uint64_t>(1, cap * 3 / 4));
@@ -1134,7 +1168,7 @@ int plan_ranges(a5x_ctx* c, const Job& J, uint64_t cap, std::vector<Range>& out,
   if ((rc = job_locate(c, J, q, res))) return rc;
   std::vector<Range> work;
   for (uint64_t k = 0; k < K; k++)
-    if (q[k + 1] > q[k]) work.push_back(range_of(J, q[k], q[k + 1], &res[3 * k], &res[3 * (k + 1)]));
+    if (q[k + 1] > q[k]) work.push_back(range_of(q[k], q[k + 1], &res[3 * k], &res[3 * (k + 1)]));
   // halve oversize ranges until every range fits
   for (int pass = 0; pass < 64; pass++) {
     std::vector<uint64_t> mid;
@@ -1155,8 +1189,8 @@ int plan_ranges(a5x_ctx* c, const Job& J, uint64_t cap, std::vector<Range>& out,
         const uint64_t lb[3] = {R.b0, R.i0, 0};
         const uint64_t* lm = &mres[3 * m];
         const uint64_t le[3] = {R.b1, R.i1, 0};
-        next.push_back(range_of(J, R.cb, mid[m], lb, lm));
-        Range H = range_of(J, mid[m], R.ce, lm, le);
+        next.push_back(range_of(R.cb, mid[m], lb, lm));
+        Range H = range_of(mid[m], R.ce, lm, le);
         H.i0 = lm[1];  // the half starts inside item lm[1]
         next.push_back(H);
         m++;
@@ -1168,6 +1202,33 @@ int plan_ranges(a5x_ctx* c, const Job& J, uint64_t cap, std::vector<Range>& out,
   }
   out.swap(work);
   return A5X_OK;
+}
+
+// The side stream picks up behind the work queued on st so far (stream and events made on
+// first use); side_join: st goes on behind the side stream's work.
+int side_fork(a5x_ctx* c, hipStream_t st) {
+  if (!c->sstream) HIPCHK(c, hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking));
+  if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(c->ev_fork, st));
+  HIPCHK(c, hipStreamWaitEvent(c->sstream, c->ev_fork, 0));
+  return A5X_OK;
+}
+
+int side_join(a5x_ctx* c, hipStream_t st) {
+  HIPCHK(c, hipEventRecord(c->ev_join, c->sstream));
+  HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
+  return A5X_OK;
+}
+
+// a located range and its output buffer into an expansion or mode-engine launch
+template <class L>
+void range_into(L& X, const Range& R, uint8_t* d_out, uint64_t out_cap) {
+  X.cand_begin = R.cb;
+  X.cand_end = R.ce;
+  X.out = d_out;
+  X.out_base = R.b0;
+  X.out_cap = out_cap;
 }
 
 // Launch the expansion of one located range into d_out (asynchronous on J.st).
@@ -1182,44 +1243,26 @@ int job_launch(a5x_ctx* c, const Job& J, const Range& R, uint8_t* d_out, uint64_
     M.cand_off = J.B.cand_off;
     M.item_begin = R.i0;
     M.item_end = R.i1;
-    M.cand_begin = R.cb;
-    M.cand_end = R.ce;
-    M.out = d_out;
-    M.out_base = R.b0;
-    M.out_cap = out_cap;
+    range_into(M, R, d_out, out_cap);
     if (!J.B.rfast) {
       HIPCHK(c, a5x_launch_mode_items(M, 1, J.st));
       return A5X_OK;
     }
     // -r FAST words: k_expand_fast on the job stream, the mode engine's items (disjoint
     // output bytes) on the side stream, joined before the range completes
-    if (!c->sstream) HIPCHK(c, hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking));
-    if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_fork, J.st));
-    HIPCHK(c, hipStreamWaitEvent(c->sstream, c->ev_fork, 0));
+    if ((rc = side_fork(c, J.st))) return rc;
     // a few mode words among many FAST ones: a small grid filters the items beside k_expand_fast
     // instead of one workgroup per 64 items (C5 -s A/B, profiles/r05g_ab_mode_items_grid_c5.txt)
     M.grid_cap = J.B.nmode * 8 < J.nw ? 2048u : 0u;
     if (J.B.nmode) HIPCHK(c, a5x_launch_mode_items(M, 1, c->sstream));  // (every word FAST: none)
     A5xExpLaunch E = exp_launch_mode(c, J.w, J.wo, J.nw, J.mn, J.mx, J.B);
-    E.cand_begin = R.cb;
-    E.cand_end = R.ce;
-    E.out = d_out;
-    E.out_base = R.b0;
-    E.out_cap = out_cap;
+    range_into(E, R, d_out, out_cap);
     HIPCHK(c, a5x_launch_expand(E, 0, J.st));
-    HIPCHK(c, hipEventRecord(c->ev_join, c->sstream));
-    HIPCHK(c, hipStreamWaitEvent(J.st, c->ev_join, 0));
-    return A5X_OK;
+    return side_join(c, J.st);
   }
   const Batch& B = J.B;
   A5xExpLaunch E = exp_launch(c, J.w, J.wo, J.nw, J.mn, J.mx, B);
-  E.cand_begin = R.cb;
-  E.cand_end = R.ce;
-  E.out = d_out;
-  E.out_base = R.b0;
-  E.out_cap = out_cap;
+  range_into(E, R, d_out, out_cap);
   // slow / BIG words: (word, SEG-candidate segment) items, slow from segs[0], BIG
   // from segs[sbound]; a word adds at most ceil(range / SEG) + 1 segments
   const uint64_t rng_segs = (R.ce - R.cb) / c->seg + 1;
@@ -1229,44 +1272,28 @@ int job_launch(a5x_ctx* c, const Job& J, const Range& R, uint8_t* d_out, uint64_
     return fail(c, A5X_E_CAPACITY, "call range needs more than 2^32 slow-path segments (lower A5X_CHUNK range)");
   if (B.nslow || B.nbig) {
     if ((rc = grow(c, c->segs, sbound + bbound + 1))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_scalars + 5, 0, 8, J.st));
+    static_assert(S_BIG_SEGS == S_SLOW_SEGS + 1, "one clear for both segment counts");
+    HIPCHK(c, hipMemsetAsync(c->d_scalars + S_SLOW_SEGS, 0, 2 * sizeof(uint32_t), J.st));
   }
   if (B.nslow)
-    HIPCHK(c, a5x_launch_segments(c->slow_list.p, c->d_scalars + 3, B.nslow, B.cand_off, R.cb, R.ce, c->seg,
-                                  c->segs.p, c->d_scalars + 5, J.st));
+    HIPCHK(c, a5x_launch_segments(c->slow_list.p, c->d_scalars + S_NSLOW, B.nslow, B.cand_off, R.cb, R.ce, c->seg,
+                                  c->segs.p, c->d_scalars + S_SLOW_SEGS, J.st));
   if (B.nbig)
-    HIPCHK(c, a5x_launch_segments(c->big_list.p, c->d_scalars + 1, B.nbig, B.cand_off, R.cb, R.ce, c->seg,
-                                  c->segs.p + sbound, c->d_scalars + 6, J.st));
-  hipStream_t side = J.st;
-  if (B.nslow || B.nbig) {
-    if (!c->sstream) HIPCHK(c, hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking));
-    if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_fork, J.st));
-    HIPCHK(c, hipStreamWaitEvent(c->sstream, c->ev_fork, 0));
-    side = c->sstream;
-  }
+    HIPCHK(c, a5x_launch_segments(c->big_list.p, c->d_scalars + S_NBIG, B.nbig, B.cand_off, R.cb, R.ce, c->seg,
+                                  c->segs.p + sbound, c->d_scalars + S_BIG_SEGS, J.st));
+  const bool forked = B.nslow || B.nbig;
+  if (forked && (rc = side_fork(c, J.st))) return rc;
   if (B.nslow) {
-    E.segs = c->segs.p; E.nsegs = c->d_scalars + 5; E.nsegs_bound = sbound;
-    HIPCHK(c, a5x_launch_expand(E, 1, side));
+    E.segs = c->segs.p; E.nsegs = c->d_scalars + S_SLOW_SEGS; E.nsegs_bound = sbound;
+    HIPCHK(c, a5x_launch_expand(E, 1, c->sstream));
   }
   if (B.nbig) {
-    E.segs = c->segs.p + sbound; E.nsegs = c->d_scalars + 6; E.nsegs_bound = bbound;
-    HIPCHK(c, a5x_launch_expand(E, 2, side));
-    if (B.nglob) HIPCHK(c, a5x_launch_expand(E, 4, side));  // pass G words of the same list
+    E.segs = c->segs.p + sbound; E.nsegs = c->d_scalars + S_BIG_SEGS; E.nsegs_bound = bbound;
+    HIPCHK(c, a5x_launch_expand(E, 2, c->sstream));
+    if (B.nglob) HIPCHK(c, a5x_launch_expand(E, 4, c->sstream));  // pass G words of the same list
   }
   HIPCHK(c, a5x_launch_expand(E, 0, J.st));
-  if (side != J.st) {
-    HIPCHK(c, hipEventRecord(c->ev_join, side));
-    HIPCHK(c, hipStreamWaitEvent(J.st, c->ev_join, 0));
-  }
-  return A5X_OK;
-}
-
-int job_open(a5x_ctx* c, Job& J, const uint8_t* d_words, const uint64_t* d_woff, uint64_t nw, int mode, int mn,
-             int mx, hipStream_t st) {
-  J.w = d_words; J.wo = d_woff; J.nw = nw; J.mode = mode; J.mn = mn; J.mx = mx; J.st = st;
-  return A5X_OK;
+  return forked ? side_join(c, J.st) : A5X_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1284,7 +1311,7 @@ A5xDigLaunch dig_launch(a5x_ctx* c) {
   D.bitmap = c->t_bitmap.p;
   D.bm_mask = c->t_bm_log2 >= 32 ? 0xffffffffu : (uint32_t)((1ull << c->t_bm_log2) - 1);
   D.table = c->t_table.p; D.tmask = c->t_tmask; D.has_zero_target = c->t_has_zero;
-  D.err = c->d_scalars + 2;
+  D.err = c->d_scalars + S_ERR;
   if (c->t_tw) {
     D.tails = c->t_tails.p; D.ztails = c->t_ztails.p; D.nztails = c->t_nz;
   }
@@ -1425,22 +1452,29 @@ int hit_full_digest(a5x_ctx* c, const a5x_hit* h, uint8_t* out) {
 
 uint32_t dig_grid(a5x_ctx* c) { return (uint32_t)std::max(1, c->cus) * 8u; }
 
+// the per-block arrays of a stream of nblk blocks (dg_blk_cnt, dg_blk_pre) and their scan's scratch
+int grow_blocks(a5x_ctx* c, uint64_t nblk) {
+  int rc;
+  if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
+      (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)))
+    return rc;
+  return A5X_OK;
+}
+
 // Line starts per stream block and their exclusive scan (dg_blk_pre, nblk + 1 entries), for any
 // of the three stream kernels: launch_op1() runs the route's op 1 into dg_blk_cnt, which is
 // grown here first.  lines (null: not wanted): the stream's line count, read back.
 template <class F>
 int stream_count_lines(a5x_ctx* c, F launch_op1, uint64_t nblk, hipStream_t st, uint64_t* lines) {
   int rc;
-  if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
-      (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)))
-    return rc;
+  if ((rc = grow_blocks(c, nblk))) return rc;
   HIPCHK(c, launch_op1());
   HIPCHK(c, a5x_launch_scan(c->dg_blk_cnt.p, c->dg_blk_cnt.p, nblk, c->dg_blk_pre.p, c->dg_blk_pre.p, c->scan_tmp.p,
-                            c->d_scalars + 2, st));
+                            c->d_scalars + S_ERR, st));
   if (lines) {
-    HIPCHK(c, hipMemcpyAsync(c->h_totals + 2, c->dg_blk_pre.p + nblk, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->h_totals + T_LINES, c->dg_blk_pre.p + nblk, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    *lines = c->h_totals[2];
+    *lines = c->h_totals[T_LINES];
   }
   return A5X_OK;
 }
@@ -1465,7 +1499,7 @@ int digest_lines_multi(a5x_ctx* c, L& Q, F launch, int algo, const uint8_t* d_li
                        uint64_t cap, uint32_t per_line, const char* unit, uint64_t* n_lines, hipStream_t st,
                        uint64_t* lines, unsigned long long* counter) {
   int rc;
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 64, st));
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, S_GUARD * sizeof(uint32_t), st));  // the counters before the guard record
   HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, st));
   Q.d = dig_launch(c);
   Q.d.algo = algo;
@@ -1484,7 +1518,7 @@ int digest_lines_multi(a5x_ctx* c, L& Q, F launch, int algo, const uint8_t* d_li
   Q.d.blk_pre = c->dg_blk_pre.p;
   Q.d.dig_out = d_dig;
   HIPCHK(c, launch(2));
-  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, read_scalars(c, st, S_ERR));
   HIPCHK(c, hipMemcpyAsync(counter, c->r_counter.p, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   return A5X_OK;
@@ -1492,9 +1526,6 @@ int digest_lines_multi(a5x_ctx* c, L& Q, F launch, int algo, const uint8_t* d_li
 
 static_assert(sizeof(a5x_hit) == sizeof(A5xHitRaw), "resolved device hits are copied out as a5x_hit");
 
-// a5x_expand_digest_device.  allow_fused: default-mode batches take the fused kernel
-// (the hybrid's sub-batch of non-FAST words passes false: those words are exactly the
-// ones the fused kernel skips).
 // The item range [*i0, *i1) of the -r / -s engines holding candidates [cb, ce) (ce <= the
 // batch's count, cb < ce): the words of cb and ce - 1 from k_word_of, their first items.
 int mode_item_bounds(a5x_ctx* c, const Job& J, uint64_t cb, uint64_t ce, uint64_t* i0, uint64_t* i1) {
@@ -1516,236 +1547,292 @@ int mode_item_bounds(a5x_ctx* c, const Job& J, uint64_t cb, uint64_t ce, uint64_
   return A5X_OK;
 }
 
-// Fused (or two-pass) expansion + digest + lookup of the batch's candidates [rb, re)
-// (clipped to the batch; [0, ~0) = all): hits as (word, candidate in word).
+// ---------------------------------------------------------------------------
+// The digest routes.  expand_digest prepares the batch and picks one of three: the fused
+// -r / -s / -s -r route, the fused default route (with its hybrid sub-batch), the two-pass
+// range loop.  They share the hit buffer (HitBuf, hits_run), the target-set fields of their
+// launches (target_fields_into) and the way a call ends (digest_finish).
+// ---------------------------------------------------------------------------
+
+// One expand_digest call behind its keyspace: the candidates [rb, re) of the job's batch
+// (clipped to it) and what the caller gave for the answer.
+struct DigestCall {
+  uint64_t rb, re;
+  uint64_t scratch_bytes;
+  a5x_hit* hits;
+  uint64_t hit_cap;
+  uint64_t* n_hits;
+  a5x_stats* stats;
+  uint64_t count() const { return re - rb; }  // the candidates this call digests
+};
+
 int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uint64_t nw, int mode, int mn, int mx,
                   uint64_t rb, uint64_t re, uint64_t scratch_bytes, a5x_hit* hits, uint64_t hit_cap,
-                  uint64_t* n_hits, a5x_stats* stats, hipStream_t st, bool allow_fused, uint64_t trim = 0) {
+                  uint64_t* n_hits, a5x_stats* stats, hipStream_t st, bool allow_fused, uint64_t trim = 0);
+
+// The device hit buffer of one digest call: dg_hits, and on the two-pass route the arrays that
+// hold one record per hit beside it.  A launch counts every hit in S_NHITS and stores the
+// first n of them.
+struct HitBuf {
+  uint64_t n = 0;                    // entries
+  uint32_t tail_words = 0;           // two-pass, wide set: dg_hit_tail words per entry (0: no tails)
+  DevBuf<uint32_t>* side = nullptr;  // two-pass, rules / salts: dg_hit_rule / dg_hit_salt, one index per entry
+  bool flags_full = false;           // two-pass: the stream kernels flag a full buffer in S_ERR (STREAM_ERR_HITCAP)
+};
+
+int hits_resize(a5x_ctx* c, HitBuf& H, uint64_t n) {
   int rc;
-  // SHA-1 and the SHA-2 family: the two-pass range loop in every mode (no fused kernel hashes them)
-  const bool wide = c->t_tw != 0;
-  if (wide) {
-    allow_fused = false;
-    c->t_hit_tails.clear();
+  if ((rc = grow(c, c->dg_hits, n))) return rc;
+  if (H.tail_words && (rc = grow(c, c->dg_hit_tail, (uint64_t)H.tail_words * n))) return rc;
+  if (H.side && (rc = grow(c, *H.side, n))) return rc;
+  H.n = n;
+  return A5X_OK;
+}
+
+// the buffer's first size: the caller's, between 1024 and 2^20 entries
+int hits_open(a5x_ctx* c, HitBuf& H, uint64_t hit_cap) {
+  return hits_resize(c, H, std::max<uint64_t>(1024, std::min<uint64_t>(hit_cap, 1u << 20)));
+}
+
+// Runs run() until its hits fit the buffer.  Each turn clears S_NHITS, then run() queues the
+// route's launch, brings the scalars back ([0, S_NHITS] at least), synchronises and checks the
+// error word; *nh is the launch's hit count.  With more hits than entries, regrow(*nh) is the
+// route's rule: the size to run again with, or one no larger than the buffer to stop.
+template <class Run, class Regrow>
+int hits_run(a5x_ctx* c, hipStream_t st, HitBuf& H, uint64_t* nh, Run run, Regrow regrow) {
+  int rc;
+  for (;;) {
+    HIPCHK(c, hipMemsetAsync(c->d_scalars + S_NHITS, 0, sizeof(uint32_t), st));
+    if ((rc = run())) return rc;
+    *nh = c->h_scalars[S_NHITS];
+    const uint64_t n = *nh > H.n ? regrow(*nh) : 0;
+    if (n <= H.n) return A5X_OK;
+    if ((rc = hits_resize(c, H, n))) return rc;
+    if (H.flags_full) HIPCHK(c, hipMemsetAsync(c->d_scalars + S_ERR, 0, sizeof(uint32_t), st));
   }
-  // a nested set (a5x_nest.h): the two-pass range loop in every mode too.  An MD5-outer one is
-  // not wide, and the fused kernels would hash it as plain MD5 / NTLM
-  if (a5x_algo_nested(c->t_algo) || fused_kind(c->t_algo) < 0) allow_fused = false;
-  // rules loaded: the two-pass range loop too, k_rules_stream in place of k_digest_stream op 0
-  const bool ruled = c->n_rules != 0;
-  if (ruled) allow_fused = false;
-  c->r_hit_rule.clear();
-  c->r_rejected = c->r_hashed = 0;
-  // a salted target set: the two-pass range loop in every mode, k_salt_stream in that place
-  // (a5x_set_rules / a5x_set_salted_targets refuse the two together)
-  const bool salted = c->salted;
-  if (salted) allow_fused = false;
-  c->s_hit_salt.clear();
-  c->s_hashed = c->s_skipped = 0;
-  Job J;
-  job_open(c, J, d_words, d_woff, nw, mode, mn, mx, st);
-  J.lengths = mode == A5X_MODE_DEFAULT || !allow_fused;  // the fused -r / -s digest needs no layout
-  if ((rc = grow(c, c->dg_cand_off, nw + 1)) || (rc = grow(c, c->dg_byte_off, nw + 1))) return rc;
-  if ((rc = job_prepare(c, J, c->dg_cand_off.p, c->dg_byte_off.p, true))) return rc;
-  const uint64_t tc_all = J.B.total_cands, tb = J.B.total_bytes;
-  re = std::min(re, tc_all - std::min(trim, tc_all));  // (trim: candidates dropped at the end)
-  rb = std::min(rb, re);
-  const bool whole = rb == 0 && re == tc_all;
-  const uint64_t tc = re - rb;  // the candidates this call digests
-  // Fused path (default mode): k_expand_fast_md5 / k_expand_fast_ntlm hash each FAST
-  // word's candidates in the LDS ring where they are built -- no HBM scratch, no second
-  // pass, hits already (word, candidate).  The other candidate-bearing words (slow / BIG
-  // / pass G) are gathered into a sub-batch for the two-pass path (hybrid).  Modes
-  // -r / -s / -s -r: the two-pass range loop below.
-  if (mode != A5X_MODE_DEFAULT && allow_fused) {
-    // -r / -s / -s -r: every item's candidates hashed where the engine builds them
-    // (positional ring or byte-builder buffer), hits as (word, candidate) directly
-    uint64_t dev_hits = std::max<uint64_t>(1024, std::min<uint64_t>(hit_cap, 1u << 20));
-    if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
-    uint64_t nh = 0;
-    float ms = 0;
-    uint64_t it0 = 0, it1 = c->m_items;  // the items holding [rb, re)
-    if (!whole && tc && (rc = mode_item_bounds(c, J, rb, re, &it0, &it1))) return rc;
-    for (;;) {
-      A5xModeLaunch M = mode_launch(c, J.w, J.wo, J.nw, J.mode, J.mn, J.mx, J.B.rfast);
-      const A5xDigLaunch D = dig_launch(c);
-      M.cand_off = J.B.cand_off;
-      M.item_begin = it0;
-      M.item_end = tc ? it1 : it0;
-      M.cand_begin = rb;
-      M.cand_end = re;
-      M.dg_algo = c->t_algo;
-      M.dg_bitmap = D.bitmap; M.dg_bm_mask = D.bm_mask; M.dg_has_zero = D.has_zero_target;
-      M.dg_table = D.table; M.dg_tmask = D.tmask;
-      M.dg_hits = c->dg_hits.p; M.dg_hit_cap = (uint32_t)dev_hits; M.dg_nhits = c->d_scalars + 8;
-      HIPCHK(c, hipMemsetAsync(c->d_scalars + 8, 0, 4, J.st));
-      HIPCHK(c, hipEventRecord(c->ev[1], J.st));
-      M.grid_cap = J.B.nmode * 8 < J.nw ? 2048u : 0u;  // (as in job_launch)
-      if (J.B.nmode && tc) HIPCHK(c, a5x_launch_mode_items(M, 2, J.st));
-      if (J.B.rfast && tc) {  // -r FAST words: hashed in k_expand_fast_md5 / _ntlm's ring
-        A5xExpLaunch E = exp_launch_mode(c, J.w, J.wo, J.nw, J.mn, J.mx, J.B);
-        E.cand_begin = rb;
-        E.cand_end = re;
-        E.dg_bitmap = D.bitmap; E.dg_bm_mask = D.bm_mask; E.dg_has_zero = D.has_zero_target;
-        E.dg_table = D.table; E.dg_tmask = D.tmask;
-        E.dg_hits = c->dg_hits.p; E.dg_hit_cap = (uint32_t)dev_hits; E.dg_nhits = c->d_scalars + 8;
-        HIPCHK(c, a5x_launch_expand(E, fused_kind(c->t_algo), J.st));
-      }
-      HIPCHK(c, hipEventRecord(c->ev[2], J.st));
-      HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, J.st));
-      HIPCHK(c, hipStreamSynchronize(J.st));
-      HIPCHK(c, hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
-      if ((rc = decode_dev_err(c, c->h_scalars[2]))) return rc;
-      nh = c->h_scalars[8];
-      if (nh <= dev_hits || hit_cap <= dev_hits) break;
-      dev_hits = std::min<uint64_t>(nh, hit_cap);  // run again with room for every hit the caller takes
-      if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
-    }
-    const uint64_t take = std::min(std::min(nh, dev_hits), hit_cap);
-    if (take) {
-      HIPCHK(c, hipMemcpyAsync(hits, c->dg_hits.p, take * sizeof(a5x_hit), hipMemcpyDeviceToHost, J.st));
-      HIPCHK(c, hipStreamSynchronize(J.st));
-    }
-    float a = 0;
-    HIPCHK(c, hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
-    a5x_stats total;
-    memset(&total, 0, sizeof total);
-    total.words = nw;
-    total.candidates = tc;
-    total.expand_launches = 1;
-    total.ms_keyspace = a;
-    total.ms_expand = ms;  // build + digest + lookup, fused
-    total.ms_total = a + ms;
-    if (n_hits) *n_hits = nh;
-    if (stats) *stats = total;
-    if (nh > hit_cap)
-      return fail(c, A5X_E_CAPACITY, "%llu hits, buffer has %llu", (unsigned long long)nh, (unsigned long long)hit_cap);
-    return A5X_OK;
+}
+
+// the target set and the hit buffer into the dg_* fields of an expansion or mode-engine launch
+template <class L>
+void target_fields_into(a5x_ctx* c, L& X, const HitBuf& H) {
+  const A5xDigLaunch D = dig_launch(c);
+  X.dg_bitmap = D.bitmap; X.dg_bm_mask = D.bm_mask; X.dg_has_zero = D.has_zero_target;
+  X.dg_table = D.table; X.dg_tmask = D.tmask;
+  X.dg_hits = c->dg_hits.p; X.dg_hit_cap = (uint32_t)H.n; X.dg_nhits = c->d_scalars + S_NHITS;
+}
+
+// The hits of a fused route: launch(H) queues the route's kernels between ev[1] and ev[2], as
+// often as hits_run asks.  The fused kernels write (word, candidate) hits and never flag a
+// full buffer, so the error word is checked whole, and a second run has room for every hit the
+// caller takes: min(found, hit_cap), which stops once the buffer has hit_cap entries.
+// *ms: the last run's time; *take: the hits copied to the caller, the first of *nh found.
+template <class Launch>
+int fused_hits(a5x_ctx* c, hipStream_t st, const DigestCall& Q, Launch launch, uint64_t* nh, uint64_t* take,
+               float* ms) {
+  int rc;
+  HitBuf H;
+  if ((rc = hits_open(c, H, Q.hit_cap))) return rc;
+  auto run = [&]() -> int {
+    int rc;
+    if ((rc = launch(H))) return rc;
+    HIPCHK(c, read_scalars(c, st, S_NHITS));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipEventElapsedTime(ms, c->ev[1], c->ev[2]));
+    return decode_dev_err(c, c->h_scalars[S_ERR]);
+  };
+  if ((rc = hits_run(c, st, H, nh, run, [&](uint64_t found) { return std::min(found, Q.hit_cap); }))) return rc;
+  *take = std::min(std::min(*nh, H.n), Q.hit_cap);
+  if (*take) {
+    HIPCHK(c, hipMemcpyAsync(Q.hits, c->dg_hits.p, *take * sizeof(a5x_hit), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
   }
-  const bool fused = mode == A5X_MODE_DEFAULT && tc > 0 && allow_fused;
-  const bool hybrid = fused && (J.B.nslow || J.B.nbig || J.B.nglob);
-  if (fused) {
-    uint64_t dev_hits = std::max<uint64_t>(1024, std::min<uint64_t>(hit_cap, 1u << 20));
-    if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
-    uint64_t nh = 0;
-    float ms = 0;
-    for (;;) {
-      A5xExpLaunch E = exp_launch(c, J.w, J.wo, J.nw, J.mn, J.mx, J.B);
-      const A5xDigLaunch D = dig_launch(c);
-      E.cand_begin = rb;
-      E.cand_end = re;
-      E.dg_bitmap = D.bitmap; E.dg_bm_mask = D.bm_mask; E.dg_has_zero = D.has_zero_target;
-      E.dg_table = D.table; E.dg_tmask = D.tmask;
-      E.dg_hits = c->dg_hits.p; E.dg_hit_cap = (uint32_t)dev_hits; E.dg_nhits = c->d_scalars + 8;
-      HIPCHK(c, hipMemsetAsync(c->d_scalars + 8, 0, 4, J.st));
-      HIPCHK(c, hipEventRecord(c->ev[1], J.st));
+  return A5X_OK;
+}
+
+a5x_stats digest_stats(const Job& J, const DigestCall& Q) {
+  a5x_stats s;
+  memset(&s, 0, sizeof s);
+  s.words = J.nw;
+  s.candidates = Q.count();
+  return s;
+}
+
+// how every route ends: the hit count, the stats, and A5X_E_CAPACITY for hits the caller's buffer had no room for
+int digest_finish(a5x_ctx* c, const DigestCall& Q, uint64_t found, const a5x_stats& total) {
+  if (Q.n_hits) *Q.n_hits = found;
+  if (Q.stats) *Q.stats = total;
+  if (found > Q.hit_cap)
+    return fail(c, A5X_E_CAPACITY, "%llu hits, buffer has %llu", (unsigned long long)found,
+                (unsigned long long)Q.hit_cap);
+  return A5X_OK;
+}
+
+// Fused -r / -s / -s -r route: every item's candidates hashed where the engine builds them
+// (positional ring or byte-builder buffer), the FAST words' in k_expand_fast_md5 / _ntlm's
+// ring; hits as (word, candidate) directly.  No output layout, so stats.bytes stays 0.
+int digest_fused_modes(a5x_ctx* c, const Job& J, const DigestCall& Q) {
+  int rc;
+  const uint64_t tc = Q.count();
+  uint64_t it0 = 0, it1 = c->m_items;  // the items holding [rb, re)
+  const bool whole = Q.rb == 0 && Q.re == J.B.total_cands;
+  if (!whole && tc && (rc = mode_item_bounds(c, J, Q.rb, Q.re, &it0, &it1))) return rc;
+  auto launch = [&](const HitBuf& H) -> int {
+    A5xModeLaunch M = mode_launch(c, J.w, J.wo, J.nw, J.mode, J.mn, J.mx, J.B.rfast);
+    M.cand_off = J.B.cand_off;
+    M.item_begin = it0;
+    M.item_end = tc ? it1 : it0;
+    M.cand_begin = Q.rb;
+    M.cand_end = Q.re;
+    M.dg_algo = c->t_algo;
+    target_fields_into(c, M, H);
+    HIPCHK(c, hipEventRecord(c->ev[1], J.st));
+    M.grid_cap = J.B.nmode * 8 < J.nw ? 2048u : 0u;  // (as in job_launch)
+    if (J.B.nmode && tc) HIPCHK(c, a5x_launch_mode_items(M, 2, J.st));
+    if (J.B.rfast && tc) {
+      A5xExpLaunch E = exp_launch_mode(c, J.w, J.wo, J.nw, J.mn, J.mx, J.B);
+      E.cand_begin = Q.rb;
+      E.cand_end = Q.re;
+      target_fields_into(c, E, H);
       HIPCHK(c, a5x_launch_expand(E, fused_kind(c->t_algo), J.st));
-      HIPCHK(c, hipEventRecord(c->ev[2], J.st));
-      HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, J.st));
-      HIPCHK(c, hipStreamSynchronize(J.st));
-      HIPCHK(c, hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
-      if ((rc = decode_dev_err(c, c->h_scalars[2]))) return rc;
-      nh = c->h_scalars[8];
-      if (nh <= dev_hits || hit_cap <= dev_hits) break;
-      dev_hits = std::min<uint64_t>(nh, hit_cap);  // run again with room for every hit the caller takes
-      if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
     }
-    uint64_t take = std::min(std::min(nh, dev_hits), hit_cap);
-    if (take) {
-      HIPCHK(c, hipMemcpyAsync(hits, c->dg_hits.p, take * sizeof(a5x_hit), hipMemcpyDeviceToHost, J.st));
-      HIPCHK(c, hipStreamSynchronize(J.st));
-    }
-    float a = 0;  // this batch's keyspace (before the sub-batch reuses the events)
-    HIPCHK(c, hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
-    float ms_sub = 0;
-    if (hybrid) {
-      // The words the fused kernel skipped, in batch order, as a compact sub-batch in
-      // the context's hybrid buffers (sized with grow(): no per-call allocation).
-      // Host memory touched with device-produced values: idx[] (sized by the device count
-      // m, itself bounded by nw) and the caller's hits[take, take + got) with got <= room.
-      if ((rc = grow(c, c->hy_list, std::max<uint64_t>(1, nw)))) return rc;
-      HIPCHK(c, hipMemsetAsync(c->d_scalars + 9, 0, 4, J.st));
-      HIPCHK(c, a5x_launch_nonfast_list(c->flags.p, J.B.cand_off, nw, rb, re, c->hy_list.p, c->d_scalars + 9, J.st));
-      HIPCHK(c, hipMemcpyAsync(c->h_scalars + 9, c->d_scalars + 9, 4, hipMemcpyDeviceToHost, J.st));
-      HIPCHK(c, hipStreamSynchronize(J.st));
-      const uint32_t m = c->h_scalars[9];
-      if (m > nw) return fail(c, A5X_E_HIP, "non-FAST word list of %u words in a batch of %llu", m, (unsigned long long)nw);
-      std::vector<uint32_t> idx(m);
-      std::vector<uint64_t> off((size_t)m + 1, 0);
-      if ((rc = grow(c, c->hy_lens, (size_t)m + 1)) || (rc = grow(c, c->hy_off, (size_t)m + 1))) return rc;
-      if (m) {
-        HIPCHK(c, hipMemcpyAsync(idx.data(), c->hy_list.p, (size_t)m * 4, hipMemcpyDeviceToHost, J.st));
-        HIPCHK(c, hipStreamSynchronize(J.st));
-        std::sort(idx.begin(), idx.end());
-        HIPCHK(c, hipMemcpyAsync(c->hy_list.p, idx.data(), (size_t)m * 4, hipMemcpyHostToDevice, J.st));
-        HIPCHK(c, a5x_launch_gather_words(J.w, J.wo, c->hy_list.p, m, c->hy_lens.p, nullptr, nullptr, J.st));
-        HIPCHK(c, hipMemcpyAsync(off.data() + 1, c->hy_lens.p, (size_t)m * 8, hipMemcpyDeviceToHost, J.st));
-        HIPCHK(c, hipStreamSynchronize(J.st));
-        for (uint32_t k = 0; k < m; k++) off[k + 1] += off[k];
-      }
-      if ((rc = grow(c, c->hy_words, off[m] + 16))) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->hy_off.p, off.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, J.st));
-      HIPCHK(c, hipMemsetAsync(c->hy_words.p, 0, off[m] + 16, J.st));
-      HIPCHK(c, a5x_launch_gather_words(J.w, J.wo, c->hy_list.p, m, nullptr, c->hy_off.p, c->hy_words.p, J.st));
-      // their candidates through the two-pass path; hit word indices mapped back to the batch.
-      // A word cut by [rb, re) (the first / last listed): only its part inside the range --
-      // the sub-batch range drops the candidates before rb and after re.
-      uint64_t sb = 0, se_cut = 0;
-      if (m && !whole) {
-        uint64_t c0 = 0, c1 = 0;
-        HIPCHK(c, hipMemcpyAsync(&c0, J.B.cand_off + idx[0], 8, hipMemcpyDeviceToHost, J.st));
-        HIPCHK(c, hipMemcpyAsync(&c1, J.B.cand_off + idx[m - 1] + 1, 8, hipMemcpyDeviceToHost, J.st));
-        HIPCHK(c, hipStreamSynchronize(J.st));
-        sb = rb > c0 ? rb - c0 : 0;
-        se_cut = c1 > re ? c1 - re : 0;
-      }
-      const uint64_t room = hit_cap > take ? hit_cap - take : 0;
-      uint64_t nh2 = 0;
-      a5x_stats st2;
-      memset(&st2, 0, sizeof st2);
-      rc = expand_digest(c, c->hy_words.p, c->hy_off.p, m, mode, mn, mx, sb, ~0ull, scratch_bytes,
-                         room ? hits + take : nullptr, room, &nh2, &st2, J.st, false, se_cut);
-      if (rc && rc != A5X_E_CAPACITY) return rc;
-      const uint64_t got = std::min(nh2, room);
-      for (uint64_t i = take; i < take + got; i++) {
-        if (hits[i].word >= m)
-          return fail(c, A5X_E_HIP, "sub-batch hit word %llu of %u", (unsigned long long)hits[i].word, m);
-        hits[i].word = idx[hits[i].word];
-      }
-      take += got;
-      nh += nh2;
-      ms_sub = st2.ms_total;
-    }
-    a5x_stats total;
-    memset(&total, 0, sizeof total);
-    total.words = nw;
-    total.candidates = tc;
-    total.bytes = tb;
-    total.expand_launches = 1;
-    total.ms_keyspace = a;
-    total.ms_expand = ms + ms_sub;  // expansion + digest + lookup: fused (+ the two-pass sub-batch)
-    total.ms_total = a + ms + ms_sub;
-    if (n_hits) *n_hits = nh;
-    if (stats) *stats = total;
-    if (nh > hit_cap)
-      return fail(c, A5X_E_CAPACITY, "%llu hits, buffer has %llu", (unsigned long long)nh,
-                  (unsigned long long)hit_cap);
+    HIPCHK(c, hipEventRecord(c->ev[2], J.st));
     return A5X_OK;
+  };
+  uint64_t nh = 0, take = 0;
+  float ms = 0, ms_ks = 0;
+  if ((rc = fused_hits(c, J.st, Q, launch, &nh, &take, &ms))) return rc;
+  HIPCHK(c, hipEventElapsedTime(&ms_ks, c->ev[0], c->ev[1]));
+  a5x_stats total = digest_stats(J, Q);
+  total.expand_launches = 1;
+  total.ms_keyspace = ms_ks;
+  total.ms_expand = ms;  // build + digest + lookup, fused
+  total.ms_total = ms_ks + ms;
+  return digest_finish(c, Q, nh, total);
+}
+
+// The hybrid's sub-batch: the candidate-bearing words the fused kernel skipped (slow / BIG /
+// pass G), in batch order, as a compact batch in the context's hybrid buffers (sized with
+// grow(): no per-call allocation), through the two-pass route; its hits land behind the *take
+// the caller already has, their word indices mapped back to the batch.
+// Host memory touched with device-produced values: idx[] (sized by the device count m, itself
+// bounded by nw) and the caller's hits[take, take + got) with got <= room.
+int digest_hybrid_rest(a5x_ctx* c, const Job& J, const DigestCall& Q, uint64_t* take, uint64_t* nh, float* ms_sub) {
+  int rc;
+  const uint64_t nw = J.nw;
+  if ((rc = grow(c, c->hy_list, std::max<uint64_t>(1, nw)))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->d_scalars + S_NONFAST_N, 0, sizeof(uint32_t), J.st));
+  HIPCHK(c, a5x_launch_nonfast_list(c->flags.p, J.B.cand_off, nw, Q.rb, Q.re, c->hy_list.p,
+                                    c->d_scalars + S_NONFAST_N, J.st));
+  HIPCHK(c, hipMemcpyAsync(c->h_scalars + S_NONFAST_N, c->d_scalars + S_NONFAST_N, sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, J.st));
+  HIPCHK(c, hipStreamSynchronize(J.st));
+  const uint32_t m = c->h_scalars[S_NONFAST_N];
+  if (m > nw) return fail(c, A5X_E_HIP, "non-FAST word list of %u words in a batch of %llu", m, (unsigned long long)nw);
+  std::vector<uint32_t> idx(m);
+  std::vector<uint64_t> off((size_t)m + 1, 0);
+  if ((rc = grow(c, c->hy_lens, (size_t)m + 1)) || (rc = grow(c, c->hy_off, (size_t)m + 1))) return rc;
+  if (m) {
+    HIPCHK(c, hipMemcpyAsync(idx.data(), c->hy_list.p, (size_t)m * 4, hipMemcpyDeviceToHost, J.st));
+    HIPCHK(c, hipStreamSynchronize(J.st));
+    std::sort(idx.begin(), idx.end());
+    HIPCHK(c, hipMemcpyAsync(c->hy_list.p, idx.data(), (size_t)m * 4, hipMemcpyHostToDevice, J.st));
+    HIPCHK(c, a5x_launch_gather_words(J.w, J.wo, c->hy_list.p, m, c->hy_lens.p, nullptr, nullptr, J.st));
+    HIPCHK(c, hipMemcpyAsync(off.data() + 1, c->hy_lens.p, (size_t)m * 8, hipMemcpyDeviceToHost, J.st));
+    HIPCHK(c, hipStreamSynchronize(J.st));
+    for (uint32_t k = 0; k < m; k++) off[k + 1] += off[k];
   }
-  uint64_t cap = scratch_bytes ? scratch_bytes : ((uint64_t)2 << 30);
-  cap = std::max<uint64_t>(4096, std::min<uint64_t>(cap, tb + 64));
+  if ((rc = grow(c, c->hy_words, off[m] + 16))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->hy_off.p, off.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, J.st));
+  HIPCHK(c, hipMemsetAsync(c->hy_words.p, 0, off[m] + 16, J.st));
+  HIPCHK(c, a5x_launch_gather_words(J.w, J.wo, c->hy_list.p, m, nullptr, c->hy_off.p, c->hy_words.p, J.st));
+  // A word cut by [rb, re) (the first / last listed): only its part inside the range --
+  // the sub-batch range drops the candidates before rb and after re.
+  uint64_t sb = 0, se_cut = 0;
+  if (m && !(Q.rb == 0 && Q.re == J.B.total_cands)) {
+    uint64_t c0 = 0, c1 = 0;
+    HIPCHK(c, hipMemcpyAsync(&c0, J.B.cand_off + idx[0], 8, hipMemcpyDeviceToHost, J.st));
+    HIPCHK(c, hipMemcpyAsync(&c1, J.B.cand_off + idx[m - 1] + 1, 8, hipMemcpyDeviceToHost, J.st));
+    HIPCHK(c, hipStreamSynchronize(J.st));
+    sb = Q.rb > c0 ? Q.rb - c0 : 0;
+    se_cut = c1 > Q.re ? c1 - Q.re : 0;
+  }
+  const uint64_t room = Q.hit_cap > *take ? Q.hit_cap - *take : 0;
+  uint64_t nh2 = 0;
+  a5x_stats st2;
+  memset(&st2, 0, sizeof st2);
+  // (allow_fused false: these words are exactly the ones the fused kernel skips)
+  rc = expand_digest(c, c->hy_words.p, c->hy_off.p, m, J.mode, J.mn, J.mx, sb, ~0ull, Q.scratch_bytes,
+                     room ? Q.hits + *take : nullptr, room, &nh2, &st2, J.st, false, se_cut);
+  if (rc && rc != A5X_E_CAPACITY) return rc;
+  const uint64_t got = std::min(nh2, room);
+  for (uint64_t i = *take; i < *take + got; i++) {
+    if (Q.hits[i].word >= m)
+      return fail(c, A5X_E_HIP, "sub-batch hit word %llu of %u", (unsigned long long)Q.hits[i].word, m);
+    Q.hits[i].word = idx[Q.hits[i].word];
+  }
+  *take += got;
+  *nh += nh2;
+  *ms_sub = st2.ms_total;
+  return A5X_OK;
+}
+
+// Fused default route: k_expand_fast_md5 / k_expand_fast_ntlm hash each FAST word's candidates
+// in the LDS ring where they are built -- no HBM scratch, no second pass, hits already
+// (word, candidate).  The other candidate-bearing words follow as the hybrid's sub-batch.
+int digest_fused_default(a5x_ctx* c, const Job& J, const DigestCall& Q) {
+  int rc;
+  auto launch = [&](const HitBuf& H) -> int {
+    A5xExpLaunch E = exp_launch(c, J.w, J.wo, J.nw, J.mn, J.mx, J.B);
+    E.cand_begin = Q.rb;
+    E.cand_end = Q.re;
+    target_fields_into(c, E, H);
+    HIPCHK(c, hipEventRecord(c->ev[1], J.st));
+    HIPCHK(c, a5x_launch_expand(E, fused_kind(c->t_algo), J.st));
+    HIPCHK(c, hipEventRecord(c->ev[2], J.st));
+    return A5X_OK;
+  };
+  uint64_t nh = 0, take = 0;
+  float ms = 0, ms_ks = 0, ms_sub = 0;
+  if ((rc = fused_hits(c, J.st, Q, launch, &nh, &take, &ms))) return rc;
+  HIPCHK(c, hipEventElapsedTime(&ms_ks, c->ev[0], c->ev[1]));  // this batch's keyspace, before the sub-batch reuses the events
+  if ((J.B.nslow || J.B.nbig || J.B.nglob) && (rc = digest_hybrid_rest(c, J, Q, &take, &nh, &ms_sub))) return rc;
+  a5x_stats total = digest_stats(J, Q);
+  total.bytes = J.B.total_bytes;
+  total.expand_launches = 1;
+  total.ms_keyspace = ms_ks;
+  total.ms_expand = ms + ms_sub;  // expansion + digest + lookup: fused (+ the two-pass sub-batch)
+  total.ms_total = ms_ks + ms + ms_sub;
+  return digest_finish(c, Q, nh, total);
+}
+
+// Two-pass route, the range loop: each range of at most scratch_bytes is expanded into HBM
+// scratch (job_launch), then a stream kernel hashes its lines -- k_digest_stream, with rules
+// k_rules_stream, with a salted set k_salt_stream.  Hits are (block, ordinal) until
+// k_hits_resolve.  A range's candidates stay in scratch, so a range with more hits than the
+// device buffer is digested again with room for all of them -- unless the caller's buffer is
+// full already, when only the count matters.
+int digest_two_pass(a5x_ctx* c, const Job& J, const DigestCall& Q) {
+  int rc;
+  const bool wide = c->t_tw != 0, ruled = c->n_rules != 0, salted = c->salted;
+  const uint64_t nw = J.nw, hit_cap = Q.hit_cap;
+  a5x_hit* const hits = Q.hits;
+  uint64_t cap = Q.scratch_bytes ? Q.scratch_bytes : ((uint64_t)2 << 30);
+  cap = std::max<uint64_t>(4096, std::min<uint64_t>(cap, J.B.total_bytes + 64));
   std::vector<Range> ranges;
-  if ((rc = plan_ranges(c, J, cap, ranges, rb, re))) return rc;
+  if ((rc = plan_ranges(c, J, cap, ranges, Q.rb, Q.re))) return rc;
   if ((rc = grow(c, c->dg_scratch, cap + 64))) return rc;
-  uint64_t dev_hits = std::max<uint64_t>(1024, std::min<uint64_t>(hit_cap, 1u << 20));
-  if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
-  const uint32_t HT = a5x_hit_tail_stride(c->t_algo);  // tail words the kernels record per hit
-  if (wide && (rc = grow(c, c->dg_hit_tail, (uint64_t)HT * dev_hits))) return rc;
-  // The route, chosen here once: the rule / salt index of every hit (device array beside the hit
-  // buffer, and the context's copy), and below the launch of the route's op 0 kernel
+  // The set's kind, chosen here once: the tail words the kernels record per hit, the rule / salt
+  // index of every hit (device array beside the hit buffer, and the context's copy), and below
+  // the launch of the kind's op 0 kernel
+  const uint32_t HT = a5x_hit_tail_stride(c->t_algo);
   DevBuf<uint32_t>* const side = ruled ? &c->dg_hit_rule : salted ? &c->dg_hit_salt : nullptr;
   std::vector<uint32_t>& side_host = ruled ? c->r_hit_rule : c->s_hit_salt;
-  if (side && ((rc = grow(c, *side, dev_hits)) || (rc = grow(c, c->r_counter, 2)))) return rc;
+  HitBuf H;
+  H.tail_words = wide ? HT : 0;
+  H.side = side;
+  H.flags_full = true;
+  if ((rc = hits_open(c, H, hit_cap))) return rc;
+  if (side && (rc = grow(c, c->r_counter, 2))) return rc;
   auto launch_op0 = [&](const A5xDigLaunch& D) -> hipError_t {
     const uint32_t cus = (uint32_t)std::max(1, c->cus);
     if (ruled) {
@@ -1759,11 +1846,8 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
     return a5x_launch_digest_stream(D, 0, dig_grid(c), J.st);
   };
   std::vector<uint32_t> htail;  // wide: the range's hit tails
-  a5x_stats total;
-  memset(&total, 0, sizeof total);
-  total.words = nw;
-  total.candidates = tc;
-  total.bytes = tb;
+  a5x_stats total = digest_stats(J, Q);
+  total.bytes = J.B.total_bytes;
   uint64_t found = 0, copied = 0;
   float ms_exp = 0, ms_dig = 0, ms_ks = 0;
   HIPCHK(c, hipEventRecord(c->ev[3], J.st));  // the keyspace (and the range plan) ends here
@@ -1777,44 +1861,34 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
     D.out = c->dg_scratch.p;
     D.nbytes = R.b1 - R.b0;
     const uint64_t nblk = side ? a5x_stream_blocks(D.nbytes) : a5x_digest_blocks(D.nbytes, D.algo);
-    if ((rc = grow(c, c->dg_blk_cnt, nblk + 1)) || (rc = grow(c, c->dg_blk_pre, nblk + 1)) ||
-        (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nblk + 1) + 16)))
-      return rc;
+    if ((rc = grow_blocks(c, nblk))) return rc;
     D.blk_cnt = c->dg_blk_cnt.p;
     uint64_t nh = 0;
     unsigned long long rej = 0;  // ruled: the range's lines longer than A5X_RULE_LMAX; salted: its skipped pairs
     {
-      float me = 0;  // the range's expansion, once (a retry below re-runs only the digest)
+      float me = 0;  // the range's expansion, once (a second run below re-runs only the digest)
       HIPCHK(c, hipEventSynchronize(c->ev[2]));
       HIPCHK(c, hipEventElapsedTime(&me, c->ev[1], c->ev[2]));
       ms_exp += me;
     }
-    for (;;) {  // a range with more hits than the device buffer is digested again with room for all
+    auto digest = [&]() -> int {
       D.hits = c->dg_hits.p;
       D.hit_tail = wide ? c->dg_hit_tail.p : nullptr;
-      D.hit_cap = (uint32_t)dev_hits;
-      D.nhits = c->d_scalars + 8;
-      HIPCHK(c, hipMemsetAsync(c->d_scalars + 8, 0, 4, J.st));
+      D.hit_cap = (uint32_t)H.n;
+      D.nhits = c->d_scalars + S_NHITS;
       if (side) HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, J.st));
       HIPCHK(c, hipEventRecord(c->dev_ev[0], J.st));
       HIPCHK(c, launch_op0(D));
       HIPCHK(c, hipEventRecord(c->dev_ev[1], J.st));
-      HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 64, hipMemcpyDeviceToHost, J.st));
+      HIPCHK(c, read_scalars(c, J.st, S_NHITS));
       if (side) HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, J.st));
       HIPCHK(c, hipStreamSynchronize(J.st));
       float md = 0;
       HIPCHK(c, hipEventElapsedTime(&md, c->dev_ev[0], c->dev_ev[1]));
       ms_dig += md;
-      const uint32_t e = c->h_scalars[2] & ~(1u << 10);
-      if ((rc = decode_dev_err(c, e))) return rc;
-      nh = c->h_scalars[8];
-      if (nh <= dev_hits || copied >= hit_cap) break;
-      dev_hits = nh;  // grow and run this range's digest again (its candidates are still in scratch)
-      if ((rc = grow(c, c->dg_hits, dev_hits))) return rc;
-      if (wide && (rc = grow(c, c->dg_hit_tail, (uint64_t)HT * dev_hits))) return rc;
-      if (side && (rc = grow(c, *side, dev_hits))) return rc;
-      HIPCHK(c, hipMemsetAsync(c->d_scalars + 2, 0, 4, J.st));
-    }
+      return decode_dev_err(c, c->h_scalars[S_ERR] & ~(1u << 10));  // (STREAM_ERR_HITCAP is hits_run's business)
+    };
+    if ((rc = hits_run(c, J.st, H, &nh, digest, [&](uint64_t n) { return copied >= hit_cap ? 0 : n; }))) return rc;
     if (salted) {
       const uint64_t pairs = (R.ce - R.cb) * c->n_salts;
       if (rej > pairs) return fail(c, A5X_E_HIP, "more skipped pairs than the range has");
@@ -1827,9 +1901,9 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
       c->r_hashed += (R.ce - R.cb - rej) * c->n_rules;
     }
     if (nh) {
-      const uint64_t got = std::min<uint64_t>(nh, dev_hits);
+      const uint64_t got = std::min<uint64_t>(nh, H.n);
       HIPCHK(c, a5x_launch_scan(c->dg_blk_cnt.p, c->dg_blk_cnt.p, nblk, c->dg_blk_pre.p, c->dg_blk_pre.p,
-                                c->scan_tmp.p, c->d_scalars + 2, J.st));
+                                c->scan_tmp.p, c->d_scalars + S_ERR, J.st));
       HIPCHK(c, a5x_launch_hits_resolve(c->dg_hits.p, (uint32_t)got, c->dg_blk_pre.p, R.cb, c->dg_cand_off.p, nw,
                                         J.st));
       const uint64_t take = std::min(hit_cap - std::min(hit_cap, copied), got);
@@ -1860,11 +1934,48 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   total.ms_total = total.ms_keyspace + ms_exp + ms_dig;
   total.words_slow = J.B.nslow;
   total.words_pass_b = J.B.nbig;
-  if (n_hits) *n_hits = found;
-  if (stats) *stats = total;
-  if (found > hit_cap)
-    return fail(c, A5X_E_CAPACITY, "%llu hits, buffer has %llu", (unsigned long long)found,
-                (unsigned long long)hit_cap);
+  return digest_finish(c, Q, found, total);
+}
+
+// Expansion + digest + lookup of the batch's candidates [rb, re) (clipped to the batch;
+// [0, ~0) = all, less the last trim): hits as (word, candidate in word).  allow_fused: the
+// caller's wish (A5X_NO_FUSED_DIGEST; the hybrid's sub-batch passes false).
+int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uint64_t nw, int mode, int mn, int mx,
+                  uint64_t rb, uint64_t re, uint64_t scratch_bytes, a5x_hit* hits, uint64_t hit_cap,
+                  uint64_t* n_hits, a5x_stats* stats, hipStream_t st, bool allow_fused, uint64_t trim) {
+  int rc;
+  // what the latest call's hits left in the context: the tails of hits on a shared prefix (wide
+  // sets), each hit's rule and the rule counts, each hit's salt and the pair counts
+  if (c->t_tw) c->t_hit_tails.clear();
+  c->r_hit_rule.clear();
+  c->r_rejected = c->r_hashed = 0;
+  c->s_hit_salt.clear();
+  c->s_hashed = c->s_skipped = 0;
+  // The fused kernels hash plain MD5 and NTLM only.  The two-pass range loop in every mode for:
+  // a wide set (SHA-1 and the SHA-2 family); a nested one (a5x_nest.h -- an MD5-outer one is not
+  // wide, and the fused kernels would hash it as plain MD5); rules loaded (k_rules_stream); a
+  // salted set (k_salt_stream; a5x_set_rules / a5x_set_salted_targets refuse the two together)
+  if (c->t_tw || a5x_algo_nested(c->t_algo) || fused_kind(c->t_algo) < 0 || c->n_rules || c->salted) allow_fused = false;
+  Job J{d_words, d_woff, nw, mode, mn, mx, st};
+  J.lengths = mode == A5X_MODE_DEFAULT || !allow_fused;  // the fused -r / -s digest needs no layout
+  if ((rc = grow(c, c->dg_cand_off, nw + 1)) || (rc = grow(c, c->dg_byte_off, nw + 1))) return rc;
+  if ((rc = job_prepare(c, J, c->dg_cand_off.p, c->dg_byte_off.p, true))) return rc;  // (records ev[0])
+  const uint64_t tc_all = J.B.total_cands;
+  re = std::min(re, tc_all - std::min(trim, tc_all));  // (trim: candidates dropped at the end)
+  rb = std::min(rb, re);
+  const DigestCall Q{rb, re, scratch_bytes, hits, hit_cap, n_hits, stats};
+  if (allow_fused && mode != A5X_MODE_DEFAULT) return digest_fused_modes(c, J, Q);
+  if (allow_fused && Q.count() > 0) return digest_fused_default(c, J, Q);
+  return digest_two_pass(c, J, Q);
+}
+
+// host words and offsets of a batch into the context's staging buffers (s_words, s_woff), on its stream
+int stage_words(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw) {
+  int rc;
+  const uint64_t wbytes = nw ? woff[nw] : 0;
+  if ((rc = grow(c, c->s_words, wbytes + 16)) || (rc = grow(c, c->s_woff, nw + 1))) return rc;
+  if (wbytes) HIPCHK(c, hipMemcpyAsync(c->s_words.p, words, wbytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->s_woff.p, woff, (nw + 1) * 8, hipMemcpyHostToDevice, c->stream));
   return A5X_OK;
 }
 
@@ -1928,9 +2039,9 @@ int a5x_create(int device, a5x_ctx** out) {
   }
   if (c->cus <= 0) c->cus = 256;
   const char* what = nullptr;
-  if ((e = hipMalloc((void**)&c->d_scalars, 256)) != hipSuccess) what = "hipMalloc";
-  else if ((e = hipHostMalloc((void**)&c->h_scalars, 256, 0)) != hipSuccess) what = "hipHostMalloc";
-  else if ((e = hipHostMalloc((void**)&c->h_totals, 64, 0)) != hipSuccess) what = "hipHostMalloc";
+  if ((e = hipMalloc((void**)&c->d_scalars, S_ALLOC * sizeof(uint32_t))) != hipSuccess) what = "hipMalloc";
+  else if ((e = hipHostMalloc((void**)&c->h_scalars, S_ALLOC * sizeof(uint32_t), 0)) != hipSuccess) what = "hipHostMalloc";
+  else if ((e = hipHostMalloc((void**)&c->h_totals, T_ALLOC * sizeof(uint64_t), 0)) != hipSuccess) what = "hipHostMalloc";
   else if ((e = a5x_set_kernel_attrs()) != hipSuccess) what = "hipFuncSetAttribute";
   for (int i = 0; i < 4 && !what; i++)
     if ((e = hipEventCreate(&c->ev[i])) != hipSuccess) what = "hipEventCreate";
@@ -2143,8 +2254,7 @@ int a5x_expand_device(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
   int rc;
   if ((rc = check_mode(c, mode))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  Job J;
-  job_open(c, J, d_words, d_woff, nw, mode, mn, mx, stream ? (hipStream_t)stream : c->stream);
+  Job J{d_words, d_woff, nw, mode, mn, mx, stream ? (hipStream_t)stream : c->stream};
   if ((rc = job_prepare(c, J, d_cand_off, d_byte_off, true))) return rc;
   const Batch& B = J.B;
   const uint64_t cb = std::min(cand_begin, B.total_cands);
@@ -2158,7 +2268,7 @@ int a5x_expand_device(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
   if (cb > 0 || ce < B.total_cands) {
     std::vector<uint64_t> res;
     if ((rc = job_locate(c, J, {cb, ce}, res))) return rc;
-    R = range_of(J, cb, ce, &res[0], &res[3]);
+    R = range_of(cb, ce, &res[0], &res[3]);
   }
   if (stats) {
     stats->candidates = ce - cb;
@@ -2191,8 +2301,7 @@ int a5x_locate_device(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
   int rc;
   if ((rc = check_mode(c, mode))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  Job J;
-  job_open(c, J, d_words, d_woff, nw, mode, mn, mx, stream ? (hipStream_t)stream : c->stream);
+  Job J{d_words, d_woff, nw, mode, mn, mx, stream ? (hipStream_t)stream : c->stream};
   if ((rc = job_prepare(c, J, nullptr, nullptr, false))) return rc;
   std::vector<uint64_t> q(n), res;
   for (uint64_t i = 0; i < n; i++) q[i] = std::min(cands[i], J.B.total_cands);
@@ -2210,8 +2319,7 @@ int a5x_split_device(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff,
   int rc;
   if ((rc = check_mode(c, mode))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  Job J;
-  job_open(c, J, d_words, d_woff, nw, mode, mn, mx, stream ? (hipStream_t)stream : c->stream);
+  Job J{d_words, d_woff, nw, mode, mn, mx, stream ? (hipStream_t)stream : c->stream};
   if ((rc = job_prepare(c, J, nullptr, nullptr, false))) return rc;
   const uint64_t T = J.B.total_cands, TB = J.B.total_bytes;
   // lockstep binary searches: lo[i] < answer <= hi[i], byte(g) = first byte of candidate g
@@ -2271,10 +2379,7 @@ int a5x_keyspace(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_
   int rc;
   if ((rc = check_mode(c, mode))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t wbytes = nw ? woff[nw] : 0;
-  if ((rc = grow(c, c->s_words, wbytes + 16)) || (rc = grow(c, c->s_woff, nw + 1))) return rc;
-  if (wbytes) HIPCHK(c, hipMemcpyAsync(c->s_words.p, words, wbytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->s_woff.p, woff, (nw + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if ((rc = stage_words(c, words, woff, nw))) return rc;
   Batch B;
   if (mode != A5X_MODE_DEFAULT)
     rc = run_keyspace_mode(c, c->s_words.p, c->s_woff.p, nw, mode, mn, mx, nullptr, nullptr, c->stream, &B, false);
@@ -2354,19 +2459,15 @@ int a5x_expand_range(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uin
   int rc;
   if ((rc = check_mode(c, mode))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t wbytes = nw ? woff[nw] : 0;
-  if ((rc = grow(c, c->s_words, wbytes + 16)) || (rc = grow(c, c->s_woff, nw + 1))) return rc;
-  if (wbytes) HIPCHK(c, hipMemcpyAsync(c->s_words.p, words, wbytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->s_woff.p, woff, (nw + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  Job J;
-  job_open(c, J, c->s_words.p, c->s_woff.p, nw, mode, mn, mx, c->stream);
+  if ((rc = stage_words(c, words, woff, nw))) return rc;
+  Job J{c->s_words.p, c->s_woff.p, nw, mode, mn, mx, c->stream};
   if ((rc = job_prepare(c, J, nullptr, nullptr, true))) return rc;
   const size_t cap = stream_cap();
   std::vector<Range> ranges;
   if ((rc = plan_ranges(c, J, cap, ranges, cb, ce))) return rc;
   if (!ranges.empty() && (rc = stream_buffers(c, cap))) return rc;
   // error word of each range, copied behind its launch (valid once its copy event fired)
-  uint32_t* herr = c->h_scalars + 32;
+  uint32_t* herr = c->h_scalars + H_RANGE_ERR;
   auto drain = [&](size_t k) -> int {  // range k has been copied: check it, hand it to the sink
     HIPCHK(c, hipEventSynchronize(c->ev_cpy[k & 1]));
     if (herr[k & 1]) return decode_dev_err(c, herr[k & 1]);
@@ -2379,7 +2480,7 @@ int a5x_expand_range(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uin
     const int b = (int)(k & 1);
     if (k >= 2) HIPCHK(c, hipStreamWaitEvent(J.st, c->ev_cpy[b], 0));  // range k-2's copy left buffer b
     if ((rc = job_launch(c, J, ranges[k], c->s_out[b].p, cap))) return rc;
-    HIPCHK(c, hipMemcpyAsync(herr + b, c->d_scalars + 2, 4, hipMemcpyDeviceToHost, J.st));
+    HIPCHK(c, hipMemcpyAsync(herr + b, c->d_scalars + S_ERR, 4, hipMemcpyDeviceToHost, J.st));
     HIPCHK(c, hipEventRecord(c->ev_exp[b], J.st));
     HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_exp[b], 0));
     HIPCHK(c, hipMemcpyAsync(c->h_out[b], c->s_out[b].p, ranges[k].b1 - ranges[k].b0, hipMemcpyDeviceToHost,
@@ -2425,7 +2526,7 @@ int a5x_debug_keyspace_refit(a5x_ctx* c, uint64_t* out) {
   uint32_t n = 0;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(&n, c->d_scalars + 32, 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&n, c->d_scalars + S_REFIT, 4, hipMemcpyDeviceToHost));
   *out = n;
   return A5X_OK;
 }
@@ -2446,7 +2547,7 @@ int a5x_debug_keyspace_stage(a5x_ctx* c, uint32_t* out) {
   if (!c || !out) return A5X_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, c->d_scalars + 34, 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, c->d_scalars + S_STAGE, 4, hipMemcpyDeviceToHost));
   return A5X_OK;
 }
 
@@ -2900,7 +3001,7 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
   if (skp > lines * c->n_salts) return fail(c, A5X_E_HIP, "more skipped pairs than pairs");
   c->s_skipped = skp;
   c->s_hashed = lines * c->n_salts - skp;
-  return decode_dev_err(c, c->h_scalars[2]);
+  return decode_dev_err(c, c->h_scalars[S_ERR]);
 }
 
 int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t slen, const uint8_t* msg, size_t len,
@@ -2948,15 +3049,9 @@ int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t sle
 int a5x_expand_digest_device(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uint64_t nw, int mode,
                              int mn, int mx, uint64_t scratch_bytes, a5x_hit* hits, uint64_t hit_cap,
                              uint64_t* n_hits, a5x_stats* stats, void* stream) {
-  if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
-  if (!c || (nw && (!d_words || !d_woff)) || (hit_cap && !hits)) return A5X_E_ARG;
-  if (c->t_algo < 0) return fail(c, A5X_E_ARG, "no target set (a5x_set_targets)");
-  int rc;
-  if ((rc = check_mode(c, mode))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool fused = !getenv("A5X_NO_FUSED_DIGEST");
-  return expand_digest(c, d_words, d_woff, nw, mode, mn, mx, 0, ~0ull, scratch_bytes, hits, hit_cap, n_hits, stats,
-                       stream ? (hipStream_t)stream : c->stream, fused);
+  // (the whole batch is the range [0, ~0): the same checks, the same call)
+  return a5x_expand_digest_range_device(c, d_words, d_woff, nw, mode, mn, mx, 0, ~0ull, scratch_bytes, hits, hit_cap,
+                                        n_hits, stats, stream);
 }
 
 int a5x_expand_digest_range_device(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uint64_t nw, int mode,
@@ -2978,11 +3073,8 @@ int a5x_expand_digest(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, ui
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || (nw && (!words || !woff))) return A5X_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t wbytes = nw ? woff[nw] : 0;
   int rc;
-  if ((rc = grow(c, c->s_words, wbytes + 16)) || (rc = grow(c, c->s_woff, nw + 1))) return rc;
-  if (wbytes) HIPCHK(c, hipMemcpyAsync(c->s_words.p, words, wbytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->s_woff.p, woff, (nw + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if ((rc = stage_words(c, words, woff, nw))) return rc;
   return a5x_expand_digest_device(c, c->s_words.p, c->s_woff.p, nw, mode, mn, mx, 0, hits, hit_cap, n_hits, stats,
                                   c->stream);
 }
@@ -2998,7 +3090,7 @@ int a5x_digest_lines_device(a5x_ctx* c, int algo, const uint8_t* d_lines, uint64
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   if (n_lines) *n_lines = 0;
   if (!nbytes) return A5X_OK;
-  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, 64, st));
+  HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, S_GUARD * sizeof(uint32_t), st));  // the counters before the guard record
   A5xDigLaunch D = dig_launch(c);
   D.algo = algo;
   D.out = d_lines;
@@ -3012,9 +3104,9 @@ int a5x_digest_lines_device(a5x_ctx* c, int algo, const uint8_t* d_lines, uint64
                 (unsigned long long)cap);
   D.dig_out = d_dig;
   HIPCHK(c, a5x_launch_digest_stream(D, 2, dig_grid(c), st));
-  HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, read_scalars(c, st, S_ERR));
   HIPCHK(c, hipStreamSynchronize(st));
-  return decode_dev_err(c, c->h_scalars[2]);
+  return decode_dev_err(c, c->h_scalars[S_ERR]);
 }
 
 int a5x_digest_size(int algo) {
@@ -3190,8 +3282,7 @@ static int format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, u
   if ((rc = grow(c, c->s_words, sb.size())) || (rc = grow(c, c->s_woff, m + 1))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->s_words.p, sb.data(), sb.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->s_woff.p, so.data(), (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  Job J;
-  job_open(c, J, c->s_words.p, c->s_woff.p, m, mode, mn, mx, c->stream);
+  Job J{c->s_words.p, c->s_woff.p, m, mode, mn, mx, c->stream};
   if ((rc = job_prepare(c, J, nullptr, nullptr, false))) return rc;
   std::vector<uint64_t> coff(m + 1);
   HIPCHK(c, hipMemcpyAsync(coff.data(), J.B.cand_off, (m + 1) * 8, hipMemcpyDeviceToHost, J.st));
@@ -3229,7 +3320,7 @@ static int format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, u
     const uint64_t* lb = &loc[3 * (2 * r)];
     const uint64_t* le = &loc[3 * (2 * r + 1)];
     if (le[0] - lb[0] <= (1u << 20) || runs[r].b - runs[r].a == 1) {
-      ranges.push_back(range_of(J, ug[runs[r].a], ug[runs[r].b - 1] + 1, lb, le));
+      ranges.push_back(range_of(ug[runs[r].a], ug[runs[r].b - 1] + 1, lb, le));
       rcand.push_back({runs[r].a, runs[r].b});
     } else {
       split_runs.push_back(r);
@@ -3242,7 +3333,7 @@ static int format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, u
     size_t t = 0;
     for (size_t r : split_runs)
       for (size_t i = runs[r].a; i < runs[r].b; i++, t++) {
-        ranges.push_back(range_of(J, ug[i], ug[i] + 1, &loc2[3 * (2 * t)], &loc2[3 * (2 * t + 1)]));
+        ranges.push_back(range_of(ug[i], ug[i] + 1, &loc2[3 * (2 * t)], &loc2[3 * (2 * t + 1)]));
         rcand.push_back({i, i + 1});
       }
   }
@@ -3426,7 +3517,7 @@ int a5x_digest_lines_rules_device(a5x_ctx* c, int algo, const uint8_t* d_lines, 
   if (rej > lines) return fail(c, A5X_E_HIP, "more rejected lines than lines");
   c->r_rejected = rej;
   c->r_hashed = (lines - rej) * c->n_rules;
-  return decode_dev_err(c, c->h_scalars[2]);
+  return decode_dev_err(c, c->h_scalars[S_ERR]);
 }
 
 int a5x_debug_apply_rule(const uint8_t* rule, size_t rule_len, const uint8_t* word, size_t len, uint8_t* out,
