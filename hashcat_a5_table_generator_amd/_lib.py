@@ -39,6 +39,7 @@ EXPORTS = (
     "a5x_format_hits_rules", "a5x_digest_lines_rules_device", "a5x_debug_apply_rule",
     "a5x_set_salted_targets", "a5x_load_salted_hashes", "a5x_salt_count", "a5x_salt_get", "a5x_hit_salts",
     "a5x_salts_last", "a5x_format_hits_salted", "a5x_digest_lines_salted_device", "a5x_debug_digest_salted",
+    "a5x_algo_salt_order",
     "a5x_debug_target_set",
 )
 
@@ -134,6 +135,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                                                  ctypes.POINTER(Stats), vp]
     L.a5x_digest_lines_device.argtypes = [vp, i, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
     L.a5x_digest_size.argtypes = [i]
+    if hasattr(L, "a5x_algo_salt_order"):
+        L.a5x_algo_salt_order.argtypes = [i]
     L.a5x_hit_digest.argtypes = [vp, ctypes.POINTER(Hit), vp, sz, ctypes.POINTER(sz)]
     L.a5x_debug_digest.argtypes = [i, ctypes.c_char_p, sz, vp, sz]
     L.a5x_format_plain.argtypes = [ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz)]

@@ -7,7 +7,9 @@
 //   a5x_generator <dict-file> -t <table> [-t <table> ...] [-m N] [-x N]
 //                 [--threads N] [-s] [-r] [--device N]
 //                 [--hashes <file> [--algo md5|ntlm|sha1|sha224|sha256|sha384|sha512|md5-md5|md5-md5-md5|
-//                                          md5-md5up|md5-sha1|sha1-sha1|sha1-md5|sha256-md5] [--rules <file>]
+//                                          md5-md5up|md5-sha1|sha1-sha1|sha1-md5|sha256-md5|
+//                                          md5-md5.salt|md5-salt.md5|md5-md5.md5salt|md5-md5salt.md5|
+//                                          sha1-sha1.salt|sha1-salt.sha1|sha1-md5.salt] [--rules <file>]
 //                                  [--salted=pass.salt|salt.pass [--hex-salt]]]
 //                 [--skip N] [--limit N] [--keyspace]
 //
@@ -23,6 +25,12 @@
 // numbers implies it.  Every (hash, salt) target is reported once, at its first candidate in
 // stream order, as "hash:salt:plain" (--hex-salt: the salts are hex in the file and in the
 // output).  Without --salted a ":suffix" after a hash is ignored, as before.
+//
+// The salted nested algorithms (md5-md5.salt = hashcat -m 2611 / 2711, md5-salt.md5 = 3710,
+// md5-md5.md5salt = 3910, md5-md5salt.md5 = 2811, sha1-sha1.salt = 4510, sha1-salt.sha1 = 4520,
+// sha1-md5.salt = 4710) are salted lists by themselves, each with its own order: --salted need
+// not be given, and must agree if it is.  The salt printed is the file's own (2811 / 3910 hash
+// its MD5 text; the library does that).
 //
 // --skip / --limit / --keyspace (a5x extension, SURVEY §5 checkpoint / resume): the
 // stream's candidate order does not depend on batching (a word's candidates are
@@ -73,7 +81,12 @@ static void usage(FILE* f) {
           "                                    nested, a digest of the hex text of another: md5-md5 (-m 2600),\n"
           "                                    md5-md5-md5 (-m 3500), md5-md5up (-m 4300, upper-case hex),\n"
           "                                    md5-sha1 (-m 4400), sha1-sha1 (-m 4500), sha1-md5 (-m 4700),\n"
-          "                                    sha256-md5 (-m 20800); outer-inner, not with --salted\n"
+          "                                    sha256-md5 (-m 20800); outer-inner, not with --salted;\n"
+          "                                    salted nested (FILE holds hash:salt lines, the order is the\n"
+          "                                    algorithm's own): md5-md5.salt (-m 2611 / 2711),\n"
+          "                                    md5-salt.md5 (-m 3710), md5-md5.md5salt (-m 3910),\n"
+          "                                    md5-md5salt.md5 (-m 2811), sha1-sha1.salt (-m 4510),\n"
+          "                                    sha1-salt.sha1 (-m 4520), sha1-md5.salt (-m 4710)\n"
           "      --salted=ORDER                With --hashes: FILE holds hash:salt lines; ORDER is pass.salt\n"
           "                                    (hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710) or salt.pass\n"
           "                                    (-m 20 / 120 / 1320 / 1420 / 10820 / 1720); --algo also takes\n"
@@ -399,11 +412,22 @@ int main(int argc, char** argv) {
       else if (v == "sha1-sha1" || v == "4500") algo = A5X_ALGO_SHA1_SHA1;
       else if (v == "sha1-md5" || v == "4700") algo = A5X_ALGO_SHA1_MD5;
       else if (v == "sha256-md5" || v == "20800") algo = A5X_ALGO_SHA256_MD5;
+      else if (v == "md5-md5.salt" || v == "2611" || v == "2711") algo = A5X_ALGO_MD5_MD5_SALT;
+      else if (v == "md5-salt.md5" || v == "3710") algo = A5X_ALGO_MD5_SALT_MD5;
+      else if (v == "md5-md5.md5salt" || v == "3910") algo = A5X_ALGO_MD5_MD5_MD5SALT;
+      else if (v == "md5-md5salt.md5" || v == "2811") algo = A5X_ALGO_MD5_MD5SALT_MD5;
+      else if (v == "sha1-sha1.salt" || v == "4510") algo = A5X_ALGO_SHA1_SHA1_SALT;
+      else if (v == "sha1-salt.sha1" || v == "4520") algo = A5X_ALGO_SHA1_SALT_SHA1;
+      else if (v == "sha1-md5.salt" || v == "4710") algo = A5X_ALGO_SHA1_MD5_SALT;
       else {
         fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1, sha224, sha256, sha384 or sha512, or nested:\n"
-                        "md5-md5, md5-md5-md5, md5-md5up, md5-sha1, sha1-sha1, sha1-md5 or sha256-md5\n");
+                        "md5-md5, md5-md5-md5, md5-md5up, md5-sha1, sha1-sha1, sha1-md5 or sha256-md5, or salted nested:\n"
+                        "md5-md5.salt, md5-salt.md5, md5-md5.md5salt, md5-md5salt.md5, sha1-sha1.salt, sha1-salt.sha1\n"
+                        "or sha1-md5.salt\n");
         return 80;
       }
+      // (a salted nested algorithm implies a salted list in its own order, as a salted mode number does)
+      if (a5x_algo_salt_order(algo) >= 0) mode_order = a5x_algo_salt_order(algo);
     } else if (s.rfind("--salted", 0) == 0) {
       salted = val_of("--salted");
       if (salted != "pass.salt" && salted != "salt.pass") {
@@ -477,7 +501,8 @@ int main(int argc, char** argv) {
     return 80;
   }
   if (order >= 0 && algo >= A5X_ALGO_MD5_MD5 && algo <= A5X_ALGO_SHA256_MD5) {
-    fprintf(stderr, "a5_generator: error: --salted with a nested --algo: the nested digests have no salted mode here\n");
+    fprintf(stderr, "a5_generator: error: --salted with a nested --algo: the nested digests have no salted mode here\n"
+                    "(the salted nested forms are algorithms of their own: --algo 2611, 3710, 3910, 2811, 4510, 4520, 4710)\n");
     return 80;
   }
   if (!hashes.empty() && (cursor || keyspace_only)) {

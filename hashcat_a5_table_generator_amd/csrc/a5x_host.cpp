@@ -33,6 +33,7 @@
 #include "a5x_nest.h"
 #include "a5x_rules.h"
 #include "a5x_salt.h"
+#include "a5x_salt_nest.h"
 #include "a5x_sha.h"
 
 namespace {
@@ -1319,9 +1320,11 @@ A5xDigLaunch dig_launch(a5x_ctx* c) {
 }
 
 // digest bytes per algorithm (a5x_digest_size), 0: not an algorithm
-inline uint32_t algo_size(int algo) { return 4u * a5x_algo_words(algo); }  // (4, 8 and 9..15 are unassigned)
+inline uint32_t algo_size(int algo) { return 4u * a5x_algo_words(algo); }  // (4, 8, 9..15 and 23..31 are unassigned)
 // no salted mode: NTLM and the nested algorithms
 inline bool algo_unsalted(int algo) { return algo == A5X_ALGO_NTLM || a5x_algo_nested(algo); }
+// the salted nested algorithms 32..38 (a5x_salt_nest.h): salted sets only, each with its own salt order
+inline bool algo_salted_only(int algo) { return a5x_algo_salt_nested(algo); }
 // the fused expansion kernel that hashes a narrow plain algorithm (a5x_launch_expand's kind):
 // k_expand_fast_md5 / k_expand_fast_ntlm; -1: none (wide and nested sets never get here,
 // expand_digest sends them to the two-pass route)
@@ -1841,7 +1844,9 @@ int digest_two_pass(a5x_ctx* c, const Job& J, const DigestCall& Q) {
     }
     if (salted) {  // (an empty salted set has no salt to hash under: no launch, no hit)
       const A5xSaltLaunch SL = {D, c->s_table.p, c->n_salts, c->s_order, side->p, c->r_counter.p};
-      return c->n_salts ? a5x_launch_salt_stream(SL, 0, cus, J.st) : hipSuccess;
+      if (!c->n_salts) return hipSuccess;
+      // (by the set's algorithm: its salt records are a5x_salt.h's or a5x_salt_nest.h's)
+      return algo_salted_only(c->t_algo) ? a5x_launch_salt_nest_stream(SL, 0, cus, J.st) : a5x_launch_salt_stream(SL, 0, cus, J.st);
     }
     return a5x_launch_digest_stream(D, 0, dig_grid(c), J.st);
   };
@@ -1954,7 +1959,8 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   // The fused kernels hash plain MD5 and NTLM only.  The two-pass range loop in every mode for:
   // a wide set (SHA-1 and the SHA-2 family); a nested one (a5x_nest.h -- an MD5-outer one is not
   // wide, and the fused kernels would hash it as plain MD5); rules loaded (k_rules_stream); a
-  // salted set (k_salt_stream; a5x_set_rules / a5x_set_salted_targets refuse the two together)
+  // salted set (k_salt_stream, or k_salt_nest_stream for a salted nested one, whose MD5-outer
+  // forms are not wide either; a5x_set_rules / a5x_set_salted_targets refuse the two together)
   if (c->t_tw || a5x_algo_nested(c->t_algo) || fused_kind(c->t_algo) < 0 || c->n_rules || c->salted) allow_fused = false;
   Job J{d_words, d_woff, nw, mode, mn, mx, st};
   J.lengths = mode == A5X_MODE_DEFAULT || !allow_fused;  // the fused -r / -s digest needs no layout
@@ -2777,6 +2783,8 @@ static int upload_target_set(a5x_ctx* c, int algo, uint64_t n, TargetSet& T) {
 }
 
 int a5x_set_targets(a5x_ctx* c, int algo, const uint8_t* dig, uint64_t n) {
+  if (c && algo_salted_only(algo))
+    return fail(c, A5X_E_ARG, "digest algorithm %d is salted only (a5x_set_salted_targets)", algo);
   if (c && c->device < 0) {
     clear_salts(c);  // (a host-only context keeps a salted set's host copy: dropped, as on a device context)
     return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
@@ -2800,6 +2808,8 @@ int a5x_set_salted_targets(a5x_ctx* c, int algo, int order, const uint8_t* dig, 
   if (!W || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
   if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS)
     return fail(c, A5X_E_ARG, "salt order %d: 0 is pass.salt, 1 is salt.pass", order);
+  if (algo_salted_only(algo) && order != snest_order(algo))
+    return fail(c, A5X_E_ARG, "salt order %d: digest algorithm %d places its salt by order %d", order, algo, snest_order(algo));
   if (n && (!dig || !salt_off)) return fail(c, A5X_E_ARG, "null digests or salt offsets");
   for (uint64_t i = 0; i < n; i++) {
     if (salt_off[i + 1] < salt_off[i]) return fail(c, A5X_E_ARG, "salt offsets of target %llu decrease", (unsigned long long)i);
@@ -2833,10 +2843,19 @@ int a5x_set_salted_targets(a5x_ctx* c, int algo, int order, const uint8_t* dig, 
   std::vector<uint32_t> ord(S);
   for (uint32_t i = 0; i < S; i++) ord[i] = i;
   std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return so[x + 1] - so[x] < so[y + 1] - so[y]; });
-  std::vector<uint32_t> recs((size_t)S * A5X_SALT_STRIDE, 0u);
+  // (a salted nested set: the record layout of a5x_salt_nest.h, built for this algorithm -- the
+  // padded outer message per salt, for 34 / 35 over the salt's own MD5 text; their effective
+  // salts are all 32 bytes, so the order by the caller's lengths is an order by theirs too)
+  const bool snest = algo_salted_only(algo);
+  const uint32_t stride = snest ? A5X_SNEST_STRIDE : A5X_SALT_STRIDE;
+  std::vector<uint32_t> recs((size_t)S * stride, 0u);
   for (uint32_t k = 0; k < S; k++) {
-    uint32_t* r = &recs[(size_t)k * A5X_SALT_STRIDE];
+    uint32_t* r = &recs[(size_t)k * stride];
     const uint32_t i = ord[k], sl = (uint32_t)(so[i + 1] - so[i]);
+    if (snest) {
+      snest_record(algo, sb.data() + so[i], sl, i, r);
+      continue;
+    }
     r[A5X_SALT_R_LEN] = sl;
     r[A5X_SALT_R_INDEX] = i;
     salt_mask(i, r + A5X_SALT_R_MASK);
@@ -2976,6 +2995,11 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
   if (!algo_size(algo) || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
   if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) return fail(c, A5X_E_ARG, "bad salt order %d", order);
   if (!c->salted || !c->n_salts) return fail(c, A5X_E_ARG, "no salted target set (a5x_set_salted_targets)");
+  const bool snest = algo_salted_only(algo);
+  if (snest && order != snest_order(algo))
+    return fail(c, A5X_E_ARG, "salt order %d: digest algorithm %d places its salt by order %d", order, algo, snest_order(algo));
+  if ((snest || algo_salted_only(c->t_algo)) && algo != c->t_algo)
+    return fail(c, A5X_E_ARG, "digest algorithm %d: the set's salt records are built for algorithm %d", algo, c->t_algo);
   if (((uintptr_t)d_lines & 15u) != 0) return fail(c, A5X_E_ARG, "d_lines must be 16-byte aligned");
   if (((uintptr_t)d_dig & 3u) != 0) return fail(c, A5X_E_ARG, "d_digests must be 4-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2992,7 +3016,10 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
   SL.order = order;
   SL.hit_salt = nullptr;
   SL.skipped = c->r_counter.p;
-  auto launch = [&](int op) { return a5x_launch_salt_stream(SL, op, (uint32_t)std::max(1, c->cus), st); };
+  auto launch = [&](int op) {
+    const uint32_t cus = (uint32_t)std::max(1, c->cus);
+    return snest ? a5x_launch_salt_nest_stream(SL, op, cus, st) : a5x_launch_salt_stream(SL, op, cus, st);
+  };
   uint64_t lines = 0;
   unsigned long long skp = 0;
   if ((rc = digest_lines_multi(c, SL, launch, algo, d_lines, nbytes, d_dig, cap, c->n_salts, "salts", n_lines, st, &lines,
@@ -3010,7 +3037,18 @@ int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t sle
   if (!W || algo_unsalted(algo) || (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) ||
       (!salt && slen) || (!msg && len) || !out || slen > A5X_SALT_MAX)
     return A5X_E_ARG;
+  if (algo_salted_only(algo) && order != snest_order(algo)) return A5X_E_ARG;
   if (cap < W) return A5X_E_CAPACITY;
+  if (algo_salted_only(algo)) {  // the host path of a5x_salt_nest.h: only a candidate over 128 bytes is skipped
+    if (len > A5X_RULE_LMAX) return A5X_E_UNSUPPORTED;
+    ShaBytes src;
+    src.p = msg;
+    src.n = (uint32_t)len;
+    uint32_t w[A5X_SNEST_PW], d[5];
+    if (!snest_pair_host_any(algo, src, (uint32_t)len, salt, (uint32_t)slen, w, d)) return A5X_E_ARG;
+    memcpy(out, d, W);
+    return A5X_OK;
+  }
   if (len > A5X_RULE_LMAX || !salt_fits((uint32_t)len, (uint32_t)slen)) return A5X_E_UNSUPPORTED;  // a skipped pair
   uint32_t rec[A5X_SALT_STRIDE] = {0}, w[A5X_RULE_NDW] = {0};
   rec[A5X_SALT_R_LEN] = (uint32_t)slen;
@@ -3084,6 +3122,7 @@ int a5x_digest_lines_device(a5x_ctx* c, int algo, const uint8_t* d_lines, uint64
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || (nbytes && !d_lines)) return A5X_E_ARG;
   if (!algo_size(algo)) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
+  if (algo_salted_only(algo)) return fail(c, A5X_E_ARG, "digest algorithm %d is salted only (a5x_digest_lines_salted_device)", algo);
   if (((uintptr_t)d_lines & 15u) != 0) return fail(c, A5X_E_ARG, "d_lines must be 16-byte aligned");
   if (algo_size(algo) > 16 && ((uintptr_t)d_dig & 3u) != 0) return fail(c, A5X_E_ARG, "d_digests must be 4-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));
@@ -3112,6 +3151,11 @@ int a5x_digest_lines_device(a5x_ctx* c, int algo, const uint8_t* d_lines, uint64
 int a5x_digest_size(int algo) {
   const uint32_t w = algo_size(algo);
   return w ? (int)w : A5X_E_ARG;
+}
+
+int a5x_algo_salt_order(int algo) {
+  const int o = snest_order(algo);
+  return o < 0 ? A5X_E_ARG : o;
 }
 
 int a5x_hit_digest(a5x_ctx* c, const a5x_hit* hit, uint8_t* out, size_t cap, size_t* out_len) {
@@ -3492,6 +3536,7 @@ int a5x_digest_lines_rules_device(a5x_ctx* c, int algo, const uint8_t* d_lines, 
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || (nbytes && !d_lines)) return A5X_E_ARG;
   if (!algo_size(algo)) return fail(c, A5X_E_ARG, "bad digest algorithm %d", algo);
+  if (algo_salted_only(algo)) return fail(c, A5X_E_ARG, "digest algorithm %d is salted only: no rules on it", algo);
   if (!c->n_rules) return fail(c, A5X_E_ARG, "no rules loaded (a5x_set_rules)");
   if (((uintptr_t)d_lines & 15u) != 0) return fail(c, A5X_E_ARG, "d_lines must be 16-byte aligned");
   if (((uintptr_t)d_dig & 3u) != 0) return fail(c, A5X_E_ARG, "d_digests must be 4-byte aligned");

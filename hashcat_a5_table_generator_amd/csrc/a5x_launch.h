@@ -287,7 +287,9 @@ constexpr uint32_t a5x_algo_words(int algo) {
        : algo == A5X_ALGO_SHA384 ? 12u : algo == A5X_ALGO_SHA512 ? 16u
        : algo == A5X_ALGO_MD5_MD5 || algo == A5X_ALGO_MD5_MD5_MD5 || algo == A5X_ALGO_MD5_MD5UP ||
          algo == A5X_ALGO_MD5_SHA1 ? 4u
-       : algo == A5X_ALGO_SHA1_SHA1 || algo == A5X_ALGO_SHA1_MD5 ? 5u : algo == A5X_ALGO_SHA256_MD5 ? 8u : 0u;
+       : algo == A5X_ALGO_SHA1_SHA1 || algo == A5X_ALGO_SHA1_MD5 ? 5u : algo == A5X_ALGO_SHA256_MD5 ? 8u
+       : algo >= A5X_ALGO_MD5_MD5_SALT && algo <= A5X_ALGO_MD5_MD5SALT_MD5 ? 4u    // salted nested, MD5 outside
+       : algo >= A5X_ALGO_SHA1_SHA1_SALT && algo <= A5X_ALGO_SHA1_MD5_SALT ? 5u : 0u;  // SHA-1 outside
 }
 // wider than the 16 bytes a table slot and a hit hold: tails compared and recorded
 constexpr bool a5x_algo_wide(int algo) { return a5x_algo_words(algo) > 4u; }
@@ -338,3 +340,9 @@ struct A5xSaltLaunch {
 // digest to d.dig_out at index line * nsalts + public salt index (a skipped pair's is zero)
 // (cus: the device's compute units; the grid is cus x the workgroups a CU holds at once)
 hipError_t a5x_launch_salt_stream(const A5xSaltLaunch& L, int op, uint32_t cus, hipStream_t st);
+
+// ---- salted nested target lists (a5x_salt_nest.hip) ----------------------------
+// The same launch for a set of one of the algorithms 32..38 (L.d.algo): L.salts holds records of
+// A5X_SNEST_STRIDE u32 built for that algorithm (a5x_salt_nest.h), L.order its own placement.
+// The ops are a5x_launch_salt_stream's; a pair is skipped only for a line over A5X_RULE_LMAX.
+hipError_t a5x_launch_salt_nest_stream(const A5xSaltLaunch& L, int op, uint32_t cus, hipStream_t st);

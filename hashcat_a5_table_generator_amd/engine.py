@@ -50,6 +50,14 @@ ALGO_MD5_SHA1 = 19     # md5(hex(sha1(p))) (hashcat -m 4400)
 ALGO_SHA1_SHA1 = 20    # sha1(hex(sha1(p))) (hashcat -m 4500)
 ALGO_SHA1_MD5 = 21     # sha1(hex(md5(p))) (hashcat -m 4700)
 ALGO_SHA256_MD5 = 22   # sha256(hex(md5(p))) (hashcat -m 20800)
+# (23..31 are unassigned) salted nested: salted sets only, each with its own salt order (``salt_order``)
+ALGO_MD5_MD5_SALT = 32     # md5(hex(md5(p)) + salt) (hashcat -m 2611 / 2711)
+ALGO_MD5_SALT_MD5 = 33     # md5(salt + hex(md5(p))) (hashcat -m 3710)
+ALGO_MD5_MD5_MD5SALT = 34  # md5(hex(md5(p)) + hex(md5(salt))) (hashcat -m 3910)
+ALGO_MD5_MD5SALT_MD5 = 35  # md5(hex(md5(salt)) + hex(md5(p))) (hashcat -m 2811)
+ALGO_SHA1_SHA1_SALT = 36   # sha1(hex(sha1(p)) + salt) (hashcat -m 4510)
+ALGO_SHA1_SALT_SHA1 = 37   # sha1(salt + hex(sha1(p))) (hashcat -m 4520)
+ALGO_SHA1_MD5_SALT = 38    # sha1(hex(md5(p)) + salt) (hashcat -m 4710)
 ORDER_PASS_SALT = 0  # salted sets: hash(candidate + salt), hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710
 ORDER_SALT_PASS = 1  # hash(salt + candidate), hashcat -m 20 / 120 / 1320 / 1420 / 10820 / 1720
 
@@ -63,6 +71,15 @@ def digest_size(algo: int) -> int:
     if n < 0:
         raise A5xError(n, f"bad digest algorithm {algo}")
     return n
+
+
+def salt_order(algo: int) -> int:
+    """Where a salted nested algorithm (32..38) puts its salt (``a5x_algo_salt_order``): ``ORDER_PASS_SALT``
+    for text + salt, ``ORDER_SALT_PASS`` for salt + text -- the order its salted calls must be given."""
+    o = _lib.load().a5x_algo_salt_order(algo)
+    if o < 0:
+        raise A5xError(o, f"digest algorithm {algo} has no salt order of its own")
+    return o
 
 
 def mode_of(substitute_all: bool, reverse_sub: bool) -> int:

@@ -61,10 +61,13 @@ enum {
   A5X_MODE_SUBALL_REVERSE = 3
 };
 
-/* digest algorithms of the fused digest + lookup stage.  Values 4, 8 and
- * 9..15 are unassigned and invalid (A5X_E_ARG everywhere); additions never renumber.
+/* digest algorithms of the fused digest + lookup stage.  Values 4, 8,
+ * 9..15 and 23..31 are unassigned and invalid (A5X_E_ARG everywhere); additions never renumber.
  * 16..22 are nested: a digest of the hex text of another digest, hex = lower-case ASCII
- * hex of the inner digest in its standard byte order, HEX = upper-case. */
+ * hex of the inner digest in its standard byte order, HEX = upper-case.  32..38 are salted
+ * nested: the outer digest over that hex text and a salt ("." is concatenation); they exist
+ * only as salted sets (a5x_set_salted_targets), each with its own placement of the salt
+ * (a5x_algo_salt_order). */
 enum {
   A5X_ALGO_MD5 = 0,   /* RFC 1321 over the candidate bytes (== Go crypto/md5); hashcat -m 0 */
   A5X_ALGO_NTLM = 1,  /* MD4 (RFC 1320) over UTF-16LE of the candidate ([]rune + utf16.Encode); -m 1000 */
@@ -79,12 +82,24 @@ enum {
   A5X_ALGO_MD5_SHA1 = 19,    /* md5(hex(sha1(p))); hashcat -m 4400 */
   A5X_ALGO_SHA1_SHA1 = 20,   /* sha1(hex(sha1(p))); hashcat -m 4500 */
   A5X_ALGO_SHA1_MD5 = 21,    /* sha1(hex(md5(p))); hashcat -m 4700 */
-  A5X_ALGO_SHA256_MD5 = 22   /* sha256(hex(md5(p))); hashcat -m 20800 */
+  A5X_ALGO_SHA256_MD5 = 22,  /* sha256(hex(md5(p))); hashcat -m 20800 */
+  A5X_ALGO_MD5_MD5_SALT = 32,    /* md5(hex(md5(p)) . salt); hashcat -m 2611 / 2711 */
+  A5X_ALGO_MD5_SALT_MD5 = 33,    /* md5(salt . hex(md5(p))); -m 3710 */
+  A5X_ALGO_MD5_MD5_MD5SALT = 34, /* md5(hex(md5(p)) . hex(md5(salt))); -m 3910 */
+  A5X_ALGO_MD5_MD5SALT_MD5 = 35, /* md5(hex(md5(salt)) . hex(md5(p))); -m 2811 */
+  A5X_ALGO_SHA1_SHA1_SALT = 36,  /* sha1(hex(sha1(p)) . salt); -m 4510 */
+  A5X_ALGO_SHA1_SALT_SHA1 = 37,  /* sha1(salt . hex(sha1(p))); -m 4520 */
+  A5X_ALGO_SHA1_MD5_SALT = 38    /* sha1(hex(md5(p)) . salt); -m 4710 */
 };
-/* Digest bytes of an algorithm: 16, 16, 20, 32 for 0..3, 28, 48, 64 for 5..7 and 16, 16, 16,
- * 16, 20, 20, 32 for 16..22 (the outer digest); A5X_E_ARG for anything else (4, 8 and 9..15
- * included).  Pure host function (no HIP call). */
+/* Digest bytes of an algorithm: 16, 16, 20, 32 for 0..3, 28, 48, 64 for 5..7, 16, 16, 16,
+ * 16, 20, 20, 32 for 16..22 and 16, 16, 16, 16, 20, 20, 20 for 32..38 (the outer digest);
+ * A5X_E_ARG for anything else (4, 8, 9..15 and 23..31 included).  Pure host function (no HIP
+ * call). */
 A5X_API int a5x_digest_size(int algo);
+/* Where a salted nested algorithm (32..38) puts its salt: 0 text . salt (32, 34, 36, 38), 1
+ * salt . text (33, 35, 37) -- the `order` its salted entry points must be given.  A5X_E_ARG for
+ * every other value.  Pure host function. */
+A5X_API int a5x_algo_salt_order(int algo);
 
 /* One target hit: word index in the batch, candidate index inside that word (in the
  * library's per-word candidate order, the one a5x_expand emits), digest bytes.  For an
@@ -301,7 +316,11 @@ A5X_API int a5x_debug_apply_rule(const uint8_t* rule, size_t rule_len, const uin
  * registered with the salt salt_bytes[salt_off[i] .. salt_off[i+1]) (n + 1 offsets; at most 64
  * bytes, 0 allowed: the unsalted digest; the nested algorithms 16..22 have no salted form
  * here: A5X_E_ARG, from every salted entry point).  order 0: the message is candidate + salt
- * (pass.salt), order 1: salt + candidate (salt.pass).  Salts are deduplicated; a salt's index
+ * (pass.salt), order 1: salt + candidate (salt.pass).  The salted nested algorithms 32..38 take
+ * the hex text of the candidate's inner digest in the candidate's place; order must be the
+ * algorithm's own (a5x_algo_salt_order), else A5X_E_ARG; a candidate over 128 bytes is skipped
+ * under every salt, and no pair is skipped for its salt; for 34 / 35 the library hashes the
+ * salt itself, everything public (indices, a5x_salt_get, the output) is the caller's salt.  Salts are deduplicated; a salt's index
  * is its first appearance in the caller's order.  While the set is salted every
  * a5x_expand_digest* call hashes each candidate once per distinct salt, and a digest computed
  * under one salt matches only targets registered with that salt.  A (candidate, salt) pair
@@ -337,13 +356,16 @@ A5X_API int a5x_format_hits_salted(a5x_ctx* ctx, const uint8_t* words, const uin
                                    const uint32_t* hit_salt, int hex_salt, a5x_sink_fn sink, void* user);
 /* a5x_digest_lines_device under the S salts of the context's salted set, with algo and order
  * given here: the digest of (line i, salt s) at index i * S + s; a skipped pair's digest is
- * all zero.  digests_cap counts digests (lines x S); d_digests 4-B aligned.  Verification hook. */
+ * all zero.  digests_cap counts digests (lines x S); d_digests 4-B aligned.  Verification hook.
+ * The salt records of a salted nested set (32..38) are built for its algorithm: algo must be
+ * the set's, and any other algo on such a set is A5X_E_ARG. */
 A5X_API int a5x_digest_lines_salted_device(a5x_ctx* ctx, int algo, int order, const uint8_t* d_lines, uint64_t nbytes,
                                            uint8_t* d_digests, uint64_t digests_cap, uint64_t* n_lines, void* stream);
 /* Pure host: the digest of msg + salt (order 0) or salt + msg (order 1), the message placed
  * by the a5x_salt.h code the kernel runs and hashed by the a5x_sha.h cores (MD5: an RFC 1321
  * host compression over the same padded message words).  A5X_E_UNSUPPORTED for a pair the
- * kernel would skip (len + slen > 128). */
+ * kernel would skip (len + slen > 128).  32..38: the host path of a5x_salt_nest.h (record
+ * preparation included); A5X_E_UNSUPPORTED for a candidate over 128 bytes. */
 A5X_API int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t slen, const uint8_t* msg,
                                     size_t len, uint8_t* out, size_t cap);
 
@@ -429,7 +451,8 @@ A5X_API int a5x_debug_keyspace_large_stage(a5x_ctx* ctx, int on);
 /* Test hook (CPU test suite): the digest of msg[0, len) computed on the host by the
  * __host__ __device__ core the digest kernels run (a5x_sha.h: SHA-1 and the SHA-2 family;
  * a5x_nest.h: the nested algorithms 16..22), a5x_digest_size(algo) bytes into out.
- * A5X_E_ARG for MD5 and NTLM (their cores are device code) and for every unassigned value.
+ * A5X_E_ARG for MD5 and NTLM (their cores are device code), for every unassigned value and
+ * for the salted nested algorithms 32..38 (salted only: a5x_debug_digest_salted).
  * Never called by a compute path. */
 A5X_API int a5x_debug_digest(int algo, const uint8_t* msg, size_t len, uint8_t* out, size_t cap);
 
