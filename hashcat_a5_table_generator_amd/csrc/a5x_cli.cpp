@@ -9,7 +9,8 @@
 //                 [--hashes <file> [--algo md5|ntlm|sha1|sha224|sha256|sha384|sha512|md5-md5|md5-md5-md5|
 //                                          md5-md5up|md5-sha1|sha1-sha1|sha1-md5|sha256-md5|
 //                                          md5-md5.salt|md5-salt.md5|md5-md5.md5salt|md5-md5salt.md5|
-//                                          sha1-sha1.salt|sha1-salt.sha1|sha1-md5.salt] [--rules <file>]
+//                                          sha1-sha1.salt|sha1-salt.sha1|sha1-md5.salt|
+//                                          hmac-{md5,sha1,sha256,sha512}-key-{pass,salt}] [--rules <file>]
 //                                  [--salted=pass.salt|salt.pass [--hex-salt]]]
 //                 [--skip N] [--limit N] [--keyspace]
 //
@@ -31,6 +32,10 @@
 // sha1-md5.salt = 4710) are salted lists by themselves, each with its own order: --salted need
 // not be given, and must agree if it is.  The salt printed is the file's own (2811 / 3910 hash
 // its MD5 text; the library does that).
+//
+// So are the HMAC algorithms, hmac-HASH-key-pass (the candidate is the key, the salt the message:
+// hashcat -m 50 / 150 / 1450 / 1750 for md5 / sha1 / sha256 / sha512, order pass.salt) and
+// hmac-HASH-key-salt (the salt is the key: -m 60 / 160 / 1460 / 1760, order salt.pass).
 //
 // --skip / --limit / --keyspace (a5x extension, SURVEY §5 checkpoint / resume): the
 // stream's candidate order does not depend on batching (a word's candidates are
@@ -86,7 +91,13 @@ static void usage(FILE* f) {
           "                                    algorithm's own): md5-md5.salt (-m 2611 / 2711),\n"
           "                                    md5-salt.md5 (-m 3710), md5-md5.md5salt (-m 3910),\n"
           "                                    md5-md5salt.md5 (-m 2811), sha1-sha1.salt (-m 4510),\n"
-          "                                    sha1-salt.sha1 (-m 4520), sha1-md5.salt (-m 4710)\n"
+          "                                    sha1-salt.sha1 (-m 4520), sha1-md5.salt (-m 4710);\n"
+          "                                    HMAC (FILE holds hash:salt lines), the candidate as the key:\n"
+          "                                    hmac-md5-key-pass (-m 50), hmac-sha1-key-pass (-m 150),\n"
+          "                                    hmac-sha256-key-pass (-m 1450), hmac-sha512-key-pass (-m 1750),\n"
+          "                                    or the salt as the key: hmac-md5-key-salt (-m 60),\n"
+          "                                    hmac-sha1-key-salt (-m 160), hmac-sha256-key-salt (-m 1460),\n"
+          "                                    hmac-sha512-key-salt (-m 1760)\n"
           "      --salted=ORDER                With --hashes: FILE holds hash:salt lines; ORDER is pass.salt\n"
           "                                    (hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710) or salt.pass\n"
           "                                    (-m 20 / 120 / 1320 / 1420 / 10820 / 1720); --algo also takes\n"
@@ -419,14 +430,23 @@ int main(int argc, char** argv) {
       else if (v == "sha1-sha1.salt" || v == "4510") algo = A5X_ALGO_SHA1_SHA1_SALT;
       else if (v == "sha1-salt.sha1" || v == "4520") algo = A5X_ALGO_SHA1_SALT_SHA1;
       else if (v == "sha1-md5.salt" || v == "4710") algo = A5X_ALGO_SHA1_MD5_SALT;
+      else if (v == "hmac-md5-key-pass" || v == "50") algo = A5X_ALGO_HMAC_MD5_KEY_PASS;
+      else if (v == "hmac-md5-key-salt" || v == "60") algo = A5X_ALGO_HMAC_MD5_KEY_SALT;
+      else if (v == "hmac-sha1-key-pass" || v == "150") algo = A5X_ALGO_HMAC_SHA1_KEY_PASS;
+      else if (v == "hmac-sha1-key-salt" || v == "160") algo = A5X_ALGO_HMAC_SHA1_KEY_SALT;
+      else if (v == "hmac-sha256-key-pass" || v == "1450") algo = A5X_ALGO_HMAC_SHA256_KEY_PASS;
+      else if (v == "hmac-sha256-key-salt" || v == "1460") algo = A5X_ALGO_HMAC_SHA256_KEY_SALT;
+      else if (v == "hmac-sha512-key-pass" || v == "1750") algo = A5X_ALGO_HMAC_SHA512_KEY_PASS;
+      else if (v == "hmac-sha512-key-salt" || v == "1760") algo = A5X_ALGO_HMAC_SHA512_KEY_SALT;
       else {
         fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1, sha224, sha256, sha384 or sha512, or nested:\n"
                         "md5-md5, md5-md5-md5, md5-md5up, md5-sha1, sha1-sha1, sha1-md5 or sha256-md5, or salted nested:\n"
                         "md5-md5.salt, md5-salt.md5, md5-md5.md5salt, md5-md5salt.md5, sha1-sha1.salt, sha1-salt.sha1\n"
-                        "or sha1-md5.salt\n");
+                        "or sha1-md5.salt, or HMAC: hmac-md5-key-pass, hmac-md5-key-salt, hmac-sha1-key-pass, hmac-sha1-key-salt,\n"
+                        "hmac-sha256-key-pass, hmac-sha256-key-salt, hmac-sha512-key-pass or hmac-sha512-key-salt\n");
         return 80;
       }
-      // (a salted nested algorithm implies a salted list in its own order, as a salted mode number does)
+      // (a salted nested or HMAC algorithm implies a salted list in its own order, as a salted mode number does)
       if (a5x_algo_salt_order(algo) >= 0) mode_order = a5x_algo_salt_order(algo);
     } else if (s.rfind("--salted", 0) == 0) {
       salted = val_of("--salted");

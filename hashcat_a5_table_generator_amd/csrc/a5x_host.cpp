@@ -33,6 +33,7 @@
 #include "a5x_nest.h"
 #include "a5x_rules.h"
 #include "a5x_salt.h"
+#include "a5x_hmac.h"
 #include "a5x_salt_nest.h"
 #include "a5x_sha.h"
 
@@ -1323,8 +1324,21 @@ A5xDigLaunch dig_launch(a5x_ctx* c) {
 inline uint32_t algo_size(int algo) { return 4u * a5x_algo_words(algo); }  // (4, 8, 9..15 and 23..31 are unassigned)
 // no salted mode: NTLM and the nested algorithms
 inline bool algo_unsalted(int algo) { return algo == A5X_ALGO_NTLM || a5x_algo_nested(algo); }
-// the salted nested algorithms 32..38 (a5x_salt_nest.h): salted sets only, each with its own salt order
-inline bool algo_salted_only(int algo) { return a5x_algo_salt_nested(algo); }
+// the salted nested algorithms 32..38 (a5x_salt_nest.h) and the HMAC algorithms 48..55 (a5x_hmac.h):
+// salted sets only, each with its own salt order and its own salt records
+inline bool algo_salted_only(int algo) { return a5x_algo_salt_nested(algo) || a5x_algo_hmac(algo); }
+// that order (a5x_algo_salt_order); -1: not such an algorithm
+inline int salted_only_order(int algo) { return a5x_algo_hmac(algo) ? hmac_order(algo) : snest_order(algo); }
+// u32 per record of a salted set's device salt table, by the set's kind
+inline uint32_t salt_stride(int algo) {
+  return a5x_algo_hmac(algo) ? A5X_HMAC_STRIDE : a5x_algo_salt_nested(algo) ? A5X_SNEST_STRIDE : A5X_SALT_STRIDE;
+}
+// the stream kernel of a salted set, by the algorithm its salt records were built for
+inline hipError_t launch_salted(int rec_algo, const A5xSaltLaunch& SL, int op, uint32_t cus, hipStream_t st) {
+  return a5x_algo_hmac(rec_algo) ? a5x_launch_hmac_stream(SL, op, cus, st)
+       : a5x_algo_salt_nested(rec_algo) ? a5x_launch_salt_nest_stream(SL, op, cus, st)
+                                        : a5x_launch_salt_stream(SL, op, cus, st);
+}
 // the fused expansion kernel that hashes a narrow plain algorithm (a5x_launch_expand's kind):
 // k_expand_fast_md5 / k_expand_fast_ntlm; -1: none (wide and nested sets never get here,
 // expand_digest sends them to the two-pass route)
@@ -1845,8 +1859,8 @@ int digest_two_pass(a5x_ctx* c, const Job& J, const DigestCall& Q) {
     if (salted) {  // (an empty salted set has no salt to hash under: no launch, no hit)
       const A5xSaltLaunch SL = {D, c->s_table.p, c->n_salts, c->s_order, side->p, c->r_counter.p};
       if (!c->n_salts) return hipSuccess;
-      // (by the set's algorithm: its salt records are a5x_salt.h's or a5x_salt_nest.h's)
-      return algo_salted_only(c->t_algo) ? a5x_launch_salt_nest_stream(SL, 0, cus, J.st) : a5x_launch_salt_stream(SL, 0, cus, J.st);
+      // (by the set's algorithm: its salt records are a5x_salt.h's, a5x_salt_nest.h's or a5x_hmac.h's)
+      return launch_salted(c->t_algo, SL, 0, cus, J.st);
     }
     return a5x_launch_digest_stream(D, 0, dig_grid(c), J.st);
   };
@@ -2808,8 +2822,8 @@ int a5x_set_salted_targets(a5x_ctx* c, int algo, int order, const uint8_t* dig, 
   if (!W || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
   if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS)
     return fail(c, A5X_E_ARG, "salt order %d: 0 is pass.salt, 1 is salt.pass", order);
-  if (algo_salted_only(algo) && order != snest_order(algo))
-    return fail(c, A5X_E_ARG, "salt order %d: digest algorithm %d places its salt by order %d", order, algo, snest_order(algo));
+  if (algo_salted_only(algo) && order != salted_only_order(algo))
+    return fail(c, A5X_E_ARG, "salt order %d: digest algorithm %d places its salt by order %d", order, algo, salted_only_order(algo));
   if (n && (!dig || !salt_off)) return fail(c, A5X_E_ARG, "null digests or salt offsets");
   for (uint64_t i = 0; i < n; i++) {
     if (salt_off[i + 1] < salt_off[i]) return fail(c, A5X_E_ARG, "salt offsets of target %llu decrease", (unsigned long long)i);
@@ -2846,14 +2860,19 @@ int a5x_set_salted_targets(a5x_ctx* c, int algo, int order, const uint8_t* dig, 
   // (a salted nested set: the record layout of a5x_salt_nest.h, built for this algorithm -- the
   // padded outer message per salt, for 34 / 35 over the salt's own MD5 text; their effective
   // salts are all 32 bytes, so the order by the caller's lengths is an order by theirs too)
-  const bool snest = algo_salted_only(algo);
-  const uint32_t stride = snest ? A5X_SNEST_STRIDE : A5X_SALT_STRIDE;
+  // (an HMAC set: a5x_hmac.h's, the salt's padded message or its two key states)
+  const bool snest = a5x_algo_salt_nested(algo), hmac = a5x_algo_hmac(algo);
+  const uint32_t stride = salt_stride(algo);
   std::vector<uint32_t> recs((size_t)S * stride, 0u);
   for (uint32_t k = 0; k < S; k++) {
     uint32_t* r = &recs[(size_t)k * stride];
     const uint32_t i = ord[k], sl = (uint32_t)(so[i + 1] - so[i]);
     if (snest) {
       snest_record(algo, sb.data() + so[i], sl, i, r);
+      continue;
+    }
+    if (hmac) {
+      hmac_record(algo, sb.data() + so[i], sl, i, r);
       continue;
     }
     r[A5X_SALT_R_LEN] = sl;
@@ -2995,10 +3014,10 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
   if (!algo_size(algo) || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
   if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) return fail(c, A5X_E_ARG, "bad salt order %d", order);
   if (!c->salted || !c->n_salts) return fail(c, A5X_E_ARG, "no salted target set (a5x_set_salted_targets)");
-  const bool snest = algo_salted_only(algo);
-  if (snest && order != snest_order(algo))
-    return fail(c, A5X_E_ARG, "salt order %d: digest algorithm %d places its salt by order %d", order, algo, snest_order(algo));
-  if ((snest || algo_salted_only(c->t_algo)) && algo != c->t_algo)
+  const bool own = algo_salted_only(algo);  // its own salt records: the set's algorithm only
+  if (own && order != salted_only_order(algo))
+    return fail(c, A5X_E_ARG, "salt order %d: digest algorithm %d places its salt by order %d", order, algo, salted_only_order(algo));
+  if ((own || algo_salted_only(c->t_algo)) && algo != c->t_algo)
     return fail(c, A5X_E_ARG, "digest algorithm %d: the set's salt records are built for algorithm %d", algo, c->t_algo);
   if (((uintptr_t)d_lines & 15u) != 0) return fail(c, A5X_E_ARG, "d_lines must be 16-byte aligned");
   if (((uintptr_t)d_dig & 3u) != 0) return fail(c, A5X_E_ARG, "d_digests must be 4-byte aligned");
@@ -3018,7 +3037,7 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
   SL.skipped = c->r_counter.p;
   auto launch = [&](int op) {
     const uint32_t cus = (uint32_t)std::max(1, c->cus);
-    return snest ? a5x_launch_salt_nest_stream(SL, op, cus, st) : a5x_launch_salt_stream(SL, op, cus, st);
+    return launch_salted(algo, SL, op, cus, st);
   };
   uint64_t lines = 0;
   unsigned long long skp = 0;
@@ -3037,8 +3056,18 @@ int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t sle
   if (!W || algo_unsalted(algo) || (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) ||
       (!salt && slen) || (!msg && len) || !out || slen > A5X_SALT_MAX)
     return A5X_E_ARG;
-  if (algo_salted_only(algo) && order != snest_order(algo)) return A5X_E_ARG;
+  if (algo_salted_only(algo) && order != salted_only_order(algo)) return A5X_E_ARG;
   if (cap < W) return A5X_E_CAPACITY;
+  if (a5x_algo_hmac(algo)) {  // the host path of a5x_hmac.h: only a candidate over 128 bytes is skipped
+    if (len > A5X_RULE_LMAX) return A5X_E_UNSUPPORTED;
+    ShaBytes src;
+    src.p = msg;
+    src.n = (uint32_t)len;
+    uint32_t d[16];
+    if (!hmac_pair_host_any(algo, src, (uint32_t)len, salt, (uint32_t)slen, d)) return A5X_E_ARG;
+    memcpy(out, d, W);
+    return A5X_OK;
+  }
   if (algo_salted_only(algo)) {  // the host path of a5x_salt_nest.h: only a candidate over 128 bytes is skipped
     if (len > A5X_RULE_LMAX) return A5X_E_UNSUPPORTED;
     ShaBytes src;
@@ -3154,7 +3183,7 @@ int a5x_digest_size(int algo) {
 }
 
 int a5x_algo_salt_order(int algo) {
-  const int o = snest_order(algo);
+  const int o = salted_only_order(algo);
   return o < 0 ? A5X_E_ARG : o;
 }
 

@@ -289,7 +289,11 @@ constexpr uint32_t a5x_algo_words(int algo) {
          algo == A5X_ALGO_MD5_SHA1 ? 4u
        : algo == A5X_ALGO_SHA1_SHA1 || algo == A5X_ALGO_SHA1_MD5 ? 5u : algo == A5X_ALGO_SHA256_MD5 ? 8u
        : algo >= A5X_ALGO_MD5_MD5_SALT && algo <= A5X_ALGO_MD5_MD5SALT_MD5 ? 4u    // salted nested, MD5 outside
-       : algo >= A5X_ALGO_SHA1_SHA1_SALT && algo <= A5X_ALGO_SHA1_MD5_SALT ? 5u : 0u;  // SHA-1 outside
+       : algo >= A5X_ALGO_SHA1_SHA1_SALT && algo <= A5X_ALGO_SHA1_MD5_SALT ? 5u       // SHA-1 outside
+       : algo == A5X_ALGO_HMAC_MD5_KEY_PASS || algo == A5X_ALGO_HMAC_MD5_KEY_SALT ? 4u  // HMAC: the hash's width
+       : algo == A5X_ALGO_HMAC_SHA1_KEY_PASS || algo == A5X_ALGO_HMAC_SHA1_KEY_SALT ? 5u
+       : algo == A5X_ALGO_HMAC_SHA256_KEY_PASS || algo == A5X_ALGO_HMAC_SHA256_KEY_SALT ? 8u
+       : algo == A5X_ALGO_HMAC_SHA512_KEY_PASS || algo == A5X_ALGO_HMAC_SHA512_KEY_SALT ? 16u : 0u;
 }
 // wider than the 16 bytes a table slot and a hit hold: tails compared and recorded
 constexpr bool a5x_algo_wide(int algo) { return a5x_algo_words(algo) > 4u; }
@@ -346,3 +350,10 @@ hipError_t a5x_launch_salt_stream(const A5xSaltLaunch& L, int op, uint32_t cus, 
 // A5X_SNEST_STRIDE u32 built for that algorithm (a5x_salt_nest.h), L.order its own placement.
 // The ops are a5x_launch_salt_stream's; a pair is skipped only for a line over A5X_RULE_LMAX.
 hipError_t a5x_launch_salt_nest_stream(const A5xSaltLaunch& L, int op, uint32_t cus, hipStream_t st);
+
+// ---- HMAC target lists (a5x_hmac.hip) -------------------------------------------
+// The same launch for a set of one of the algorithms 48..55 (L.d.algo): L.salts holds records of
+// A5X_HMAC_STRIDE u32 built for that algorithm (a5x_hmac.h), L.order 0 for key = pass, 1 for key
+// = salt.  The ops are a5x_launch_salt_stream's; a pair is skipped only for a line over
+// A5X_RULE_LMAX.
+hipError_t a5x_launch_hmac_stream(const A5xSaltLaunch& L, int op, uint32_t cus, hipStream_t st);

@@ -58,6 +58,15 @@ ALGO_MD5_MD5SALT_MD5 = 35  # md5(hex(md5(salt)) + hex(md5(p))) (hashcat -m 2811)
 ALGO_SHA1_SHA1_SALT = 36   # sha1(hex(sha1(p)) + salt) (hashcat -m 4510)
 ALGO_SHA1_SALT_SHA1 = 37   # sha1(salt + hex(sha1(p))) (hashcat -m 4520)
 ALGO_SHA1_MD5_SALT = 38    # sha1(hex(md5(p)) + salt) (hashcat -m 4710)
+# (39..47 are unassigned) HMAC (RFC 2104): salted sets only; key = pass has order 0, key = salt order 1 (``salt_order``)
+ALGO_HMAC_MD5_KEY_PASS = 48     # HMAC-MD5(key = candidate, salt) (hashcat -m 50)
+ALGO_HMAC_MD5_KEY_SALT = 49     # HMAC-MD5(key = salt, candidate) (hashcat -m 60)
+ALGO_HMAC_SHA1_KEY_PASS = 50    # HMAC-SHA1(key = candidate, salt) (hashcat -m 150)
+ALGO_HMAC_SHA1_KEY_SALT = 51    # HMAC-SHA1(key = salt, candidate) (hashcat -m 160)
+ALGO_HMAC_SHA256_KEY_PASS = 52  # HMAC-SHA256(key = candidate, salt) (hashcat -m 1450)
+ALGO_HMAC_SHA256_KEY_SALT = 53  # HMAC-SHA256(key = salt, candidate) (hashcat -m 1460)
+ALGO_HMAC_SHA512_KEY_PASS = 54  # HMAC-SHA512(key = candidate, salt) (hashcat -m 1750)
+ALGO_HMAC_SHA512_KEY_SALT = 55  # HMAC-SHA512(key = salt, candidate) (hashcat -m 1760)
 ORDER_PASS_SALT = 0  # salted sets: hash(candidate + salt), hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710
 ORDER_SALT_PASS = 1  # hash(salt + candidate), hashcat -m 20 / 120 / 1320 / 1420 / 10820 / 1720
 
@@ -66,7 +75,8 @@ SubMap = Dict[bytes, List[bytes]]
 
 def digest_size(algo: int) -> int:
     """Digest bytes of an algorithm (``a5x_digest_size``): 16, 16, 20, 32 for MD5, NTLM, SHA-1, SHA-256 and
-    28, 48, 64 for SHA-224, SHA-384, SHA-512; the outer digest's 16, 20 or 32 for the nested algorithms."""
+    28, 48, 64 for SHA-224, SHA-384, SHA-512; the outer digest's 16, 20 or 32 for the nested algorithms; the
+    hash's 16, 20, 32 or 64 for the HMAC algorithms."""
     n = _lib.load().a5x_digest_size(algo)
     if n < 0:
         raise A5xError(n, f"bad digest algorithm {algo}")
@@ -75,7 +85,8 @@ def digest_size(algo: int) -> int:
 
 def salt_order(algo: int) -> int:
     """Where a salted nested algorithm (32..38) puts its salt (``a5x_algo_salt_order``): ``ORDER_PASS_SALT``
-    for text + salt, ``ORDER_SALT_PASS`` for salt + text -- the order its salted calls must be given."""
+    for text + salt, ``ORDER_SALT_PASS`` for salt + text; an HMAC algorithm (48..55): ``ORDER_PASS_SALT`` for
+    key = candidate, ``ORDER_SALT_PASS`` for key = salt -- the order its salted calls must be given."""
     o = _lib.load().a5x_algo_salt_order(algo)
     if o < 0:
         raise A5xError(o, f"digest algorithm {algo} has no salt order of its own")
@@ -596,7 +607,8 @@ def apply_rule(rule: bytes, word: bytes) -> bytes:
 def debug_digest_salted(algo: int, order: int, salt: bytes, msg: bytes) -> bytes:
     """hash(msg + salt) (order 0) or hash(salt + msg) (order 1) on the host by the message
     assembly and digest cores the salt kernel runs (``a5x_debug_digest_salted``); A5xError
-    (A5X_E_UNSUPPORTED) for a pair the kernel skips: more than 128 message bytes."""
+    (A5X_E_UNSUPPORTED) for a pair the kernel skips: more than 128 message bytes.  For an HMAC
+    algorithm (48..55) ``msg`` is the candidate: the key with order 0, the message with order 1."""
     salt, msg = bytes(salt), bytes(msg)
     out = (ctypes.c_uint8 * 64)()
     check(_lib.load().a5x_debug_digest_salted(algo, order, salt, len(salt), msg, len(msg), out, 64))

@@ -67,7 +67,9 @@ enum {
  * hex of the inner digest in its standard byte order, HEX = upper-case.  32..38 are salted
  * nested: the outer digest over that hex text and a salt ("." is concatenation); they exist
  * only as salted sets (a5x_set_salted_targets), each with its own placement of the salt
- * (a5x_algo_salt_order). */
+ * (a5x_algo_salt_order).  39..47 are unassigned and invalid.  48..55 are HMAC (RFC 2104) with the
+ * candidate as the key and the salt as the message (key = pass) or the reverse (key = salt); they
+ * too exist only as salted sets, with order 0 for key = pass and 1 for key = salt. */
 enum {
   A5X_ALGO_MD5 = 0,   /* RFC 1321 over the candidate bytes (== Go crypto/md5); hashcat -m 0 */
   A5X_ALGO_NTLM = 1,  /* MD4 (RFC 1320) over UTF-16LE of the candidate ([]rune + utf16.Encode); -m 1000 */
@@ -89,15 +91,25 @@ enum {
   A5X_ALGO_MD5_MD5SALT_MD5 = 35, /* md5(hex(md5(salt)) . hex(md5(p))); -m 2811 */
   A5X_ALGO_SHA1_SHA1_SALT = 36,  /* sha1(hex(sha1(p)) . salt); -m 4510 */
   A5X_ALGO_SHA1_SALT_SHA1 = 37,  /* sha1(salt . hex(sha1(p))); -m 4520 */
-  A5X_ALGO_SHA1_MD5_SALT = 38    /* sha1(hex(md5(p)) . salt); -m 4710 */
+  A5X_ALGO_SHA1_MD5_SALT = 38,   /* sha1(hex(md5(p)) . salt); -m 4710 */
+  A5X_ALGO_HMAC_MD5_KEY_PASS = 48,    /* HMAC-MD5(K = pass, salt); hashcat -m 50 */
+  A5X_ALGO_HMAC_MD5_KEY_SALT = 49,    /* HMAC-MD5(K = salt, pass); -m 60 */
+  A5X_ALGO_HMAC_SHA1_KEY_PASS = 50,   /* HMAC-SHA1(K = pass, salt); -m 150 */
+  A5X_ALGO_HMAC_SHA1_KEY_SALT = 51,   /* HMAC-SHA1(K = salt, pass); -m 160 */
+  A5X_ALGO_HMAC_SHA256_KEY_PASS = 52, /* HMAC-SHA256(K = pass, salt); -m 1450 */
+  A5X_ALGO_HMAC_SHA256_KEY_SALT = 53, /* HMAC-SHA256(K = salt, pass); -m 1460 */
+  A5X_ALGO_HMAC_SHA512_KEY_PASS = 54, /* HMAC-SHA512(K = pass, salt); -m 1750 */
+  A5X_ALGO_HMAC_SHA512_KEY_SALT = 55  /* HMAC-SHA512(K = salt, pass); -m 1760 */
 };
 /* Digest bytes of an algorithm: 16, 16, 20, 32 for 0..3, 28, 48, 64 for 5..7, 16, 16, 16,
- * 16, 20, 20, 32 for 16..22 and 16, 16, 16, 16, 20, 20, 20 for 32..38 (the outer digest);
- * A5X_E_ARG for anything else (4, 8, 9..15 and 23..31 included).  Pure host function (no HIP
+ * 16, 20, 20, 32 for 16..22, 16, 16, 16, 16, 20, 20, 20 for 32..38 (the outer digest) and 16,
+ * 16, 20, 20, 32, 32, 64, 64 for 48..55; A5X_E_ARG for anything else (4, 8, 9..15, 23..31, 39..47
+ * and 56 on included).  Pure host function (no HIP
  * call). */
 A5X_API int a5x_digest_size(int algo);
 /* Where a salted nested algorithm (32..38) puts its salt: 0 text . salt (32, 34, 36, 38), 1
- * salt . text (33, 35, 37) -- the `order` its salted entry points must be given.  A5X_E_ARG for
+ * salt . text (33, 35, 37); an HMAC algorithm (48..55): 0 key = pass (48, 50, 52, 54), 1 key =
+ * salt (49, 51, 53, 55) -- the `order` its salted entry points must be given.  A5X_E_ARG for
  * every other value.  Pure host function. */
 A5X_API int a5x_algo_salt_order(int algo);
 
@@ -320,7 +332,13 @@ A5X_API int a5x_debug_apply_rule(const uint8_t* rule, size_t rule_len, const uin
  * the hex text of the candidate's inner digest in the candidate's place; order must be the
  * algorithm's own (a5x_algo_salt_order), else A5X_E_ARG; a candidate over 128 bytes is skipped
  * under every salt, and no pair is skipped for its salt; for 34 / 35 the library hashes the
- * salt itself, everything public (indices, a5x_salt_get, the output) is the caller's salt.  Salts are deduplicated; a salt's index
+ * salt itself, everything public (indices, a5x_salt_get, the output) is the caller's salt.
+ * The HMAC algorithms 48..55 (RFC 2104; hashcat -m 50 / 150 / 1450 / 1750 and 60 / 160 / 1460 /
+ * 1760) follow the same rules: order 0 is HMAC(key = candidate, message = salt), order 1
+ * HMAC(key = salt, message = candidate), and order must be the algorithm's own; a candidate over
+ * 128 bytes is skipped under every salt, no pair is skipped for its salt, and a candidate of
+ * 65..128 bytes used as the key of a 64-byte-block hash is replaced by its digest, as RFC 2104
+ * says.  Salts are deduplicated; a salt's index
  * is its first appearance in the caller's order.  While the set is salted every
  * a5x_expand_digest* call hashes each candidate once per distinct salt, and a digest computed
  * under one salt matches only targets registered with that salt.  A (candidate, salt) pair
@@ -357,15 +375,19 @@ A5X_API int a5x_format_hits_salted(a5x_ctx* ctx, const uint8_t* words, const uin
 /* a5x_digest_lines_device under the S salts of the context's salted set, with algo and order
  * given here: the digest of (line i, salt s) at index i * S + s; a skipped pair's digest is
  * all zero.  digests_cap counts digests (lines x S); d_digests 4-B aligned.  Verification hook.
- * The salt records of a salted nested set (32..38) are built for its algorithm: algo must be
- * the set's, and any other algo on such a set is A5X_E_ARG. */
+ * The salt records of a salted nested set (32..38) and of an HMAC set (48..55) are built for
+ * its algorithm: algo must be the set's, any other algo on such a set is A5X_E_ARG, and so is
+ * one of these algorithms on another kind of set. */
 A5X_API int a5x_digest_lines_salted_device(a5x_ctx* ctx, int algo, int order, const uint8_t* d_lines, uint64_t nbytes,
                                            uint8_t* d_digests, uint64_t digests_cap, uint64_t* n_lines, void* stream);
 /* Pure host: the digest of msg + salt (order 0) or salt + msg (order 1), the message placed
  * by the a5x_salt.h code the kernel runs and hashed by the a5x_sha.h cores (MD5: an RFC 1321
  * host compression over the same padded message words).  A5X_E_UNSUPPORTED for a pair the
  * kernel would skip (len + slen > 128).  32..38: the host path of a5x_salt_nest.h (record
- * preparation included); A5X_E_UNSUPPORTED for a candidate over 128 bytes. */
+ * preparation included); A5X_E_UNSUPPORTED for a candidate over 128 bytes.  48..55: the host
+ * path of a5x_hmac.h (record preparation, key states, inner and outer hash), salt = the salt,
+ * msg = the candidate; A5X_E_UNSUPPORTED for a candidate over 128 bytes, A5X_E_ARG for a salt
+ * over 64 bytes or the wrong order. */
 A5X_API int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t slen, const uint8_t* msg,
                                     size_t len, uint8_t* out, size_t cap);
 
