@@ -28,7 +28,7 @@ EXPORTS = (
     "a5x_split_words", "a5x_keyspace", "a5x_expand", "a5x_expand_range", "a5x_expand_device", "a5x_keyspace_device",
     "a5x_digest_device", "a5x_partition", "a5x_dev_alloc", "a5x_dev_free", "a5x_memcpy_h2d",
     "a5x_memcpy_d2h", "a5x_synchronize", "a5x_debug_stamps", "a5x_debug_plan_word", "a5x_debug_plan_sizes",
-    "a5x_debug_piece_build",
+    "a5x_debug_piece_build", "a5x_debug_cplx_build", "a5x_debug_keyspace_cplx_lean",
     "a5x_debug_keyspace_refit", "a5x_debug_keyspace_small_stage", "a5x_debug_keyspace_stage",
     "a5x_debug_keyspace_large_stage",
     "a5x_set_targets", "a5x_expand_digest", "a5x_expand_digest_device", "a5x_expand_digest_range_device",
@@ -121,6 +121,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         L.a5x_debug_plan_sizes.argtypes = [vp, vp, sz, vp]
     if hasattr(L, "a5x_debug_piece_build"):
         L.a5x_debug_piece_build.argtypes = [vp, vp, sz, vp]
+    if hasattr(L, "a5x_debug_cplx_build"):
+        L.a5x_debug_cplx_build.argtypes = [vp, vp, sz, i, i, vp]
+        L.a5x_debug_keyspace_cplx_lean.argtypes = [vp, ctypes.POINTER(u64)]
     if hasattr(L, "a5x_debug_keyspace_refit"):
         L.a5x_debug_keyspace_refit.argtypes = [vp, ctypes.POINTER(u64)]
     if hasattr(L, "a5x_debug_keyspace_stage"):

@@ -104,8 +104,9 @@ enum Slot : uint32_t {
   S_REFIT = 32,      // keyspace words walked twice (a5x_debug_keyspace_refit)
   S_TSPAN = 33,      // largest tile span of the batch (k_tile_span)
   S_STAGE = 34,      // word stage the keyspace pass used (a5x_debug_keyspace_stage)
-  S_COUNT = 35,      // device words in use
-  H_RANGE_ERR = 36,  // host image only: a5x_expand_range's error word per output buffer, [36, 37]
+  S_CPLX_LEAN = 35,  // k_keyspace_cplx: words of the lean path, of the generic one, [35, 36] (a5x_debug_keyspace_cplx_lean)
+  S_COUNT = 37,      // device words in use
+  H_RANGE_ERR = 38,  // host image only: a5x_expand_range's error word per output buffer, [38, 39]
   S_ALLOC = 64       // words allocated, device and host
 };
 static_assert(S_COUNT <= H_RANGE_ERR && H_RANGE_ERR + 2 <= S_ALLOC, "the scalar block holds every slot");
@@ -631,6 +632,7 @@ int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uin
     K.err = c->d_scalars + S_ERR;
     K.hiflag = table_lead_only(c) ? c->d_scalars + S_HIFLAG : nullptr;
     K.nrefit = c->d_scalars + S_REFIT;
+    K.ncplx_lean = c->d_scalars + S_CPLX_LEAN;
     K.small_stage = c->ks_large_only ? 0u : a5x_keyspace_small_stage(c->table_bytes);
     K.tspan = c->d_scalars + S_TSPAN; K.stage_used = c->d_scalars + S_STAGE;
     K.nslow = c->d_scalars + S_NSLOW;
@@ -2551,6 +2553,17 @@ int a5x_debug_keyspace_refit(a5x_ctx* c, uint64_t* out) {
   return A5X_OK;
 }
 
+int a5x_debug_keyspace_cplx_lean(a5x_ctx* c, uint64_t* out) {
+  if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
+  if (!c || !out) return A5X_E_ARG;
+  uint32_t n[2] = {0, 0};
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(n, c->d_scalars + S_CPLX_LEAN, 8, hipMemcpyDeviceToHost));
+  out[0] = n[0]; out[1] = n[1];
+  return A5X_OK;
+}
+
 int a5x_debug_keyspace_small_stage(a5x_ctx* c, uint32_t* out) {
   if (!c || !out) return A5X_E_ARG;
   if (c->table.keys.empty()) return fail(c, A5X_E_NOTABLE, "no substitution table loaded");
@@ -2758,6 +2771,20 @@ int a5x_debug_piece_build(a5x_ctx* c, const uint8_t* word, size_t len, uint32_t*
   std::vector<uint8_t> wb(word, word + len);
   wb.resize(len + 16, 0);
   piece_build_compare(wb.data(), (u32)len, tab_view(c->blob.data()), out);
+  return A5X_OK;
+}
+
+int a5x_debug_cplx_build(a5x_ctx* c, const uint8_t* word, size_t len, int mn, int mx, uint32_t* out) {
+  if (!c || !out || (!word && len)) return A5X_E_ARG;
+  if (len > 127) return fail(c, A5X_E_ARG, "word of %zu bytes (the complex-word check takes <= 127)", len);
+  if (c->table.keys.empty()) return fail(c, A5X_E_NOTABLE, "no substitution table loaded");
+  if (c->table_dirty || c->blob.empty()) {
+    int rc = compile_table(c);
+    if (rc) return rc;
+  }
+  std::vector<uint8_t> wb(word, word + len);
+  wb.resize(len + 16, 0);
+  cplx_build_compare(wb.data(), (u32)len, tab_view(c->blob.data()), mn, mx, out);
   return A5X_OK;
 }
 

@@ -298,6 +298,12 @@ __device__ __forceinline__ u32 wave_append(bool pred, u32* ctr) {
                   // the count pass's, so it never gave a figure)
 #endif
 
+#ifndef KC_ABL
+#define KC_ABL 0  // k_keyspace_cplx timing ablations (variant builds only, wrong output): 1 no record
+                  // build (classification only), 2 return right after the table load (the floor), 4 the
+                  // generic path for every word, 16 stop after staging the word
+#endif
+
 // k_keyspace_thread's open group holds KS_GCAP entries (a unit with more choices
 // makes the word complex: k_keyspace_cplx plans it with FW_UMAXR)
 #define KS_GCAP 8
@@ -315,6 +321,21 @@ struct DevRecSink {
   __device__ void gst(u32, u32 a, u64 v) { g[a * 256u] = v; }
   __device__ void ent(u32 i, u64 v) { if (!(KS_ABL & 4)) rec[1 + np + i] = v; }
   __device__ void desc(u32 i, u64 v) { if (!(KS_ABL & 4)) rec[1 + i] = v; }
+};
+
+// DevRecSink for k_keyspace_cplx's lean path: the word's record slot holds FW_RMAX u64, and no
+// store leaves it whatever the builder computes.
+struct DevRecSinkC {
+  u64* g;       // LDS: g[a * 256]: group descriptors (rows 0..7), a second cluster's choices (8..15)
+  u64* c;       // LDS: cluster choices c[a * 256]
+  u64* rec;     // global record base
+  u32 np;
+  __device__ u64* cbuf() const { return c; }
+  __device__ u32 cstride() const { return 256u; }
+  __device__ u64 gld(u32, u32 a) const { return g[a * 256u]; }
+  __device__ void gst(u32, u32 a, u64 v) { g[a * 256u] = v; }
+  __device__ void ent(u32 i, u64 v) { if (1u + np + i < FW_RMAX) rec[1 + np + i] = v; }
+  __device__ void desc(u32 i, u64 v) { if (1u + i < FW_RMAX) rec[1 + i] = v; }
 };
 
 // A word's column of k_keyspace_thread's unit log (LDS; PieceBuilder's unit source).
@@ -370,7 +391,7 @@ __device__ __forceinline__ u32 ks_word_once(const W& wd, u64 L64, const Tab& T, 
   if (C.ovf) atomicOr(a.err, A5X_DERR_OVF);
   if ((f & A5X_WF_DEFER) || !(f & (A5X_WF_FAST | A5X_WF_RADIX | A5X_WF_ERR_OVF)))
     f = A5X_WF_DEFER;  // capped windows, unit limits, non-FAST clusters: the DP kernel
-  if (!((f & A5X_WF_FAST) && C.count > 0 && fits)) return f;
+  if (!((f & A5X_WF_FAST) && C.count > 0 && fits) || (KC_ABL & 1)) return f;
   if (uc.full) {
     ks_build(wd, (u32)L64, T, a, f, C.count, rec, g);
     return f;
@@ -1757,14 +1778,18 @@ __global__ void __launch_bounds__(256) k_vwords_fill(VwArgs a) {
 #define KC_SLOT 48  // k_keyspace_cplx: per-lane LDS word slot (words <= KC_SLOT - 12 bytes)
 
 // The complex words of k_keyspace_thread (overlapping keys, long keys, oversize
-// tiles), one lane per listed word: the general unit walk (next_unit) on global
-// bytes; FAST records go to fixed slots after the tile regions.
-__global__ void __launch_bounds__(256) k_keyspace_cplx(KsArgs a) {
+// tiles), one lane per listed word; FAST records go to fixed slots after the tile regions.
+// A word staged in the lane's LDS slot goes by the lean path (cplx_word_lean, a5x_plan.h:
+// matches by the kmatch records, units by index, CountPlanner, a record built per piece);
+// a word that path does not hold, by its own limits alone, takes the general unit walk
+// (ks_word_once: next_unit, Planner), as does a word longer than the slot, on global bytes.
+__global__ void __launch_bounds__(256) k_keyspace_cplx(KsArgs a, u32* nlean) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const u32 tb = (a.table_bytes + 15u) & ~15u;
   u64* gbuf = (u64*)(smem + tb);
   load_table(smem, a.table, a.table_bytes);
   __syncthreads();
+  if (KC_ABL & 2) return;
   const Tab T = tab_view(smem);
   uint8_t* wst = (uint8_t*)(gbuf + 2 * 256 * FW_UMAXR);  // KC_SLOT bytes per lane
   const u32 n = *a.cplx_n;
@@ -1776,6 +1801,7 @@ __global__ void __launch_bounds__(256) k_keyspace_cplx(KsArgs a) {
     u32 f;
     u64* const rec = a.rec + a.cplx_base + (u64)i * FW_RMAX;
     const bool fits = i < a.cplx_cap;
+    bool lean = false;
     if (L64 + 12 <= KC_SLOT) {
       // the word in this lane's LDS slot (all byte loads in flight together): the unit
       // walks below re-read every byte many times
@@ -1789,13 +1815,33 @@ __global__ void __launch_bounds__(256) k_keyspace_cplx(KsArgs a) {
           if (4 * q + b < L64) v |= (u32)gp[4 * q + b] << (8 * b);
         sl[q] = v;
       }
+      if (KC_ABL & 16) continue;
       LWord lw;
       lw.base = wst; lw.off = threadIdx.x * KC_SLOT;
-      f = ks_word_once(lw, L64, T, a, C, fits, rec, gbuf + threadIdx.x);
+      // the lean path (cplx_word_lean); a word it does not hold is walked by ks_word_once
+      DevRecSinkC sk;
+      sk.g = gbuf + threadIdx.x; sk.c = sk.g + 256 * FW_UMAXR; sk.rec = rec; sk.np = 0;
+      bool built = false, bad = false;
+      u64 rec0 = 0;
+      if (!(KC_ABL & 4))
+        lean = cplx_word_lean(lw, (u32)L64, T, a.mn, a.mx, A5X_RING_A - 16, fits && !(KC_ABL & 1), sk, C, f, built, rec0,
+                              bad) == 0u;
+      if (lean) {
+        if (C.ovf) atomicOr(a.err, A5X_DERR_OVF);
+        if (built) rec[0] = rec0;
+        if (bad) atomicOr(a.err, A5X_DERR_STATE);
+      } else {
+        f = ks_word_once(lw, L64, T, a, C, fits, rec, gbuf + threadIdx.x);
+      }
     } else {
       GWord gw;
       gw.p = a.words + s;
       f = ks_word_once(gw, L64, T, a, C, fits, rec, gbuf + threadIdx.x);
+    }
+    if (nlean) {  // {lean, generic} words of the pass (a5x_debug_keyspace_cplx_lean; null: not counted)
+      const u64 lm = __ballot(lean), fm = __ballot(!lean);
+      if (lm && lane_id() == (u32)__builtin_ctzll(lm)) atomicAdd(nlean, (u32)__popcll(lm));
+      if (fm && lane_id() == (u32)__builtin_ctzll(fm)) atomicAdd(nlean + 1, (u32)__popcll(fm));
     }
     if ((f & A5X_WF_FAST) && C.count > 0) {
       if (fits) a.roff[w] = (u32)(a.cplx_base + (u64)i * FW_RMAX);
@@ -3577,7 +3623,7 @@ hipError_t a5x_launch_keyspace(const A5xKsLaunch& L, hipStream_t st) {
     return hipGetLastError();
   }
   hipLaunchKernelGGL(k_keyspace_cplx, dim3(L.defer_blocks), dim3(256),
-                     ((L.table_bytes + 15u) & ~15u) + 2 * 256 * FW_UMAXR * 8 + 256 * KC_SLOT, st, a);
+                     ((L.table_bytes + 15u) & ~15u) + 2 * 256 * FW_UMAXR * 8 + 256 * KC_SLOT, st, a, L.ncplx_lean);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const size_t lds = ((L.table_bytes + 15u) & ~15u) + sizeof(LdsB);

@@ -57,6 +57,7 @@ struct A5xKsLaunch {
   uint32_t* tspan;       // zeroed u32: the batch's largest tile span, which picks the stage (null: the large one only)
   uint32_t* stage_used;  // u32: the stage of the k_keyspace_thread launch that did the work (null: not reported)
   uint32_t* nrefit;      // zeroed u32: k_keyspace_thread counts the words it walked with the fused psk_walk (null: no count)
+  uint32_t* ncplx_lean;  // two zeroed u32: k_keyspace_cplx counts the words of its lean and of its generic path (null: no count)
 };
 
 // the virtual word list of a batch with virtual words (k_vwords_fill)

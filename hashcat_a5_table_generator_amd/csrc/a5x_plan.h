@@ -1165,6 +1165,539 @@ A5X_HD WordClass classify_word(const W& wd, u32 L, const Tab& T, int mn, int mx,
 }
 
 // ---------------------------------------------------------------------------
+// k_keyspace_cplx's lean path: what k_keyspace_thread does for words of lone units
+// (detection by the kmatch records, CountPlanner, a record built per piece), with clusters.
+// A word the limits below do not hold (why != 0) takes the generic path (ks_word_once:
+// next_unit, Planner); the decision is the word's own.
+// ---------------------------------------------------------------------------
+#ifndef CL_ABL
+#define CL_ABL 0    // timing ablation (variant builds only, wrong output): 1 no cluster enumeration in the count pass
+#endif
+#define CL_ULOG 16  // logged units per word
+#define CL_NCL 2    // clusters per word
+#define CL_LMAX 36  // word bytes (k_keyspace_cplx's LDS slot)
+enum {
+  CL_WHY_LONGKEY = 1,   // a key longer than 4 bytes at a position it fits
+  CL_WHY_UNITS = 2,     // more than CL_ULOG units
+  CL_WHY_POS = 4,       // a unit at byte 64 or later
+  CL_WHY_KEY = 8,       // a key index >= 1024 (or a table of more than 65536 choices)
+  CL_WHY_CLUSTER = 16,  // a cluster that is not ok (FW_UMAXM matches, FW_UMAXR choices of <= FW_PLEN bytes)
+  CL_WHY_NCL = 32,      // more than CL_NCL clusters
+  CL_WHY_SLOT = 64      // a word longer than CL_LMAX
+};
+
+// The units of a word: entry i = s << 10 | key (lone match) or s << 10 | span (cluster, bit i of
+// cmask), 16 bits each in ul[i / 4]; the matches (Unit::m0 / m1) and k | R << 4 | ml << 12 of
+// the clusters.  Registers: every index below is resolved by selects.
+struct CplxLog {
+  u64 ul0, ul1, ul2, ul3;
+  u64 m0[CL_NCL], m1[CL_NCL];
+  u32 st[CL_NCL];
+  u32 n, nc, cmask, why;
+  A5X_HD CplxLog() {
+    n = 0; nc = 0; cmask = 0; why = 0;
+    ul0 = 0; ul1 = 0; ul2 = 0; ul3 = 0;
+    for (u32 j = 0; j < CL_NCL; j++) { m0[j] = 0; m1[j] = 0; st[j] = 0; }
+  }
+  A5X_HD u32 operator()(u32 i) const {
+    // (masks, not selects: a select between the four is folded into one read at a selected
+    // address, and a log read that way lives in scratch memory)
+    const u32 j = i >> 2;
+    const u64 v = (ul0 & (0ull - (u64)(j == 0))) | (ul1 & (0ull - (u64)(j == 1))) | (ul2 & (0ull - (u64)(j == 2))) |
+                  (ul3 & (0ull - (u64)(j == 3)));
+    return (u32)(v >> (16u * (i & 3u))) & 0xFFFFu;
+  }
+  A5X_HD void put(u32 i, u32 e) {
+    const u64 f = (u64)(e & 0xFFFFu) << (16u * (i & 3u));
+    const u32 j = i >> 2;
+    ul0 |= j == 0 ? f : 0ull; ul1 |= j == 1 ? f : 0ull; ul2 |= j == 2 ? f : 0ull; ul3 |= j == 3 ? f : 0ull;
+  }
+  A5X_HD bool is_cluster(u32 i) const { return (cmask >> i) & 1u; }
+  A5X_HD u32 cluster_of(u32 i) const { return (u32)__builtin_popcount(cmask & ((1u << i) - 1u)); }
+  // unit i, a cluster (ordinal ci) with the statistics the planners' cuts read (R, ml); the
+  // count pass takes the rest from cluster_choices
+  A5X_HD void get(const Tab& T, u32 i, Unit& U) const {
+    const u32 e = (*this)(i), s = e >> 10;
+    if (!is_cluster(i)) { lone_unit(T, s, e & 1023u, U); return; }
+    const u32 ci = cluster_of(i);
+    u64 a = 0, b = 0;
+    u32 c = 0;
+#pragma unroll
+    for (u32 j = 0; j < CL_NCL; j++)
+      if (j == ci) { a = m0[j]; b = m1[j]; c = st[j]; }
+    U.s = s; U.e = s + (e & 1023u);
+    U.k = c & 15u; U.nm = U.k; U.key = ~0u; U.cb = 0;
+    U.R = (c >> 4) & 255u; U.ml = (c >> 12) & 15u; U.mnl = 0; U.spos = 0; U.sneg = 0; U.maxd = 0;
+    U.m0 = a; U.m1 = b; U.ok = true;
+  }
+  A5X_HD void set_stats(u32 ci, const Unit& U) {
+#pragma unroll
+    for (u32 j = 0; j < CL_NCL; j++)
+      if (j == ci) st[j] = (U.k & 15u) | ((U.R & 255u) << 4) | ((U.ml & 15u) << 12);
+  }
+};
+
+// cluster_choices(target -2) for the lean path: the same choices in the same order with the
+// same statistics.  cluster_choices reads the key record of every match again for every subset
+// and every choice (its validity loop, its byte loop, its odometer) and copies the span byte by
+// byte, each a dependent LDS round trip: on C3 that enumeration was two thirds of
+// k_keyspace_cplx's time.  Here the matches' facts are read once into byte fields (start and
+// end inside the span, value count, the earlier matches each one overlaps), a subset is tested
+// with those masks, and a choice is put together from <= 7-byte reads of the span and the
+// table's cval records.  Needs choice indices below 65536 (CplxDetect checks the table).
+template <class W>
+A5X_HD void cluster_enum(const W& wd, Unit& U, const Tab& T, u64* content, u32 cstride) {
+  const u32 span = U.e - U.s, k = U.k;
+  u64 PS = 0, PE = 0, NV = 0, CF = 0, CB0 = 0, CB1 = 0;
+  for (u32 j = 0; j < k && j < FW_UMAXM; j++) {
+    const A5xKey& key = T.keys[unit_mkey(U, j)];
+    const u32 ps = unit_mpos(U, j) - U.s, pe = ps + key.klen;
+    u32 cf = 0;
+    for (u32 i = 0; i < j; i++) cf |= ((u32)(PE >> (8 * i)) & 255u) > ps ? 1u << i : 0u;
+    PS |= (u64)(ps & 255u) << (8 * j); PE |= (u64)(pe & 255u) << (8 * j);
+    NV |= (u64)umin32(key.nvals, 255u) << (8 * j); CF |= (u64)cf << (8 * j);
+    const u64 cb = (u64)(key.choice_base & 0xFFFFu) << (16 * (j & 3u));
+    if (j < 4) CB0 |= cb; else CB1 |= cb;
+  }
+  u32 R = 0, ml = 0, mnl = 0xffffffffu, spos = 0, sneg = 0;
+  int maxd = -(int)span;
+  bool ok = U.ok;
+  for (u32 mask = 0; mask < (1u << k) && ok; mask++) {
+    u32 bad = 0;  // chosen matches that overlap an earlier chosen one
+    for (u32 m = mask; m; m &= m - 1u) bad |= (u32)(CF >> (8 * (u32)__builtin_ctz(m))) & mask;
+    if (bad & 255u) continue;
+    u32 odo = 0;
+    while (true) {
+      u64 v = 0;
+      u32 n = 0, cur = 0;
+      for (u32 m = mask; m; m &= m - 1u) {
+        const u32 j = (u32)__builtin_ctz(m), pj = (u32)(PS >> (8 * j)) & 255u;
+        if (pj > cur) {
+          if (n < 8) v |= wd.ld(U.s + cur, umin32(pj - cur, 7u)) << (8 * n);
+          n += pj - cur;
+        }
+        const u32 ci = ((u32)((j < 4 ? CB0 : CB1) >> (16 * (j & 3u))) & 0xFFFFu) + 1u + ((odo >> (4 * j)) & 15u);
+        const u32 cl = T.ch[ci].len;
+        if (n < 8) v |= (T.cval[ci] & FW_M56) << (8 * n);
+        n += cl;
+        cur = (u32)(PE >> (8 * j)) & 255u;
+      }
+      if (span > cur) {
+        if (n < 8) v |= wd.ld(U.s + cur, umin32(span - cur, 7u)) << (8 * n);
+        n += span - cur;
+      }
+      if (n > FW_PLEN || R >= FW_UMAXR) { ok = false; break; }
+      content[R * cstride] = keep_bytes64(v, n) | ((u64)n << 56);
+      R++;
+      ml = umax32(ml, n);
+      mnl = umin32(mnl, n);
+      if (n > span) spos += n - span; else sneg += span - n;
+      maxd = (int)n - (int)span > maxd ? (int)n - (int)span : maxd;
+      bool more = false;  // next value combination, the first chosen match fastest
+      for (u32 m = mask; m && !more; m &= m - 1u) {
+        const u32 j = (u32)__builtin_ctz(m), dj = ((odo >> (4 * j)) & 15u) + 1u;
+        odo &= ~(15u << (4 * j));
+        if (dj < ((u32)(NV >> (8 * j)) & 255u) && dj < 16u) { odo |= dj << (4 * j); more = true; }
+      }
+      if (!more) break;
+    }
+  }
+  U.R = R; U.ml = ml; U.mnl = mnl; U.spos = spos; U.sneg = sneg; U.maxd = maxd; U.ok = ok;
+}
+
+// next_unit's grouping of the matches, position by position: at(q) takes the matches that start
+// at q, in key order (the bucket's); a match inside the open unit's span joins it and grows it,
+// any other closes it and opens the next.  finish() closes the last.
+template <class W>
+struct CplxDetect {
+  const W& wd;
+  const Tab& T;
+  CplxLog& lg;
+  u32 L;
+  u32 us, ue, unm, k0;
+  u64 um0, um1;
+  A5X_HD CplxDetect(const W& w, u32 l, const Tab& t, CplxLog& g) : wd(w), T(t), lg(g), L(l) {
+    us = 0; ue = 0; unm = 0; k0 = 0; um0 = 0; um1 = 0;
+    if (L > CL_LMAX) lg.why |= CL_WHY_SLOT;
+    if (T.hdr->nchoices > 65536u) lg.why |= CL_WHY_KEY;  // (cluster_enum's 16-bit choice indices)
+  }
+  A5X_HD void close() {
+    if (!unm) return;
+    const bool isc = unm > 1;
+    if (lg.n >= CL_ULOG) lg.why |= CL_WHY_UNITS;
+    if (us >= 64u) lg.why |= CL_WHY_POS;
+    if (isc && lg.nc >= CL_NCL) lg.why |= CL_WHY_NCL;
+    if (isc && unm > FW_UMAXM) lg.why |= CL_WHY_CLUSTER;
+    if (lg.n < CL_ULOG) {
+      lg.put(lg.n, ((us & 63u) << 10) | ((isc ? ue - us : k0) & 1023u));
+      if (isc) {
+        lg.cmask |= 1u << lg.n;
+#pragma unroll
+        for (u32 j = 0; j < CL_NCL; j++)
+          if (j == lg.nc) { lg.m0[j] = um0; lg.m1[j] = um1; lg.st[j] = umin32(unm, 15u); }
+        lg.nc++;
+      }
+      lg.n++;
+    }
+    unm = 0;
+  }
+  A5X_HD void match(u32 q, u32 kk, u32 kl) {
+    if (kk >= 1024u) lg.why |= CL_WHY_KEY;
+    if (unm && q < ue) {
+      if (unm < FW_UMAXM && q - us < 64u) {
+        const u64 f = (u64)(((q - us) << 10) | (kk & 1023u)) << (16u * (unm & 3u));
+        if (unm < 4) um0 |= f; else um1 |= f;
+      } else
+        lg.why |= CL_WHY_CLUSTER;
+      unm++;
+      ue = umax32(ue, q + kl);
+    } else {
+      close();
+      us = q; ue = q + kl; unm = 1; k0 = kk;
+      um0 = kk & 1023u; um1 = 0;
+    }
+  }
+  A5X_HD void at(u32 q) {
+    const u32 w4 = (u32)wd.ld(q, umin32(4u, L - q));
+    const u32 bk = T.bucket2[w4 & 255u];
+    for (u32 kk = bk & 0xFFFFu; kk < (bk >> 16); kk++) {
+      const u64 km = T.kmatch[kk];
+      const u32 kl = (u32)(km >> 32) & 0xFFFFu;
+      if (q + kl > L) continue;
+      if (kl > 4) { lg.why |= CL_WHY_LONGKEY; continue; }
+      const u32 m = kl >= 4 ? 0xFFFFFFFFu : ((1u << (8 * kl)) - 1u);
+      if ((w4 & m) == (u32)km) match(q, kk, kl);
+    }
+  }
+  A5X_HD void finish() { close(); }
+};
+
+// PieceBuilder for the units of a CplxLog: groups of <= FW_UMAXR entries (Planner's CAP of
+// k_keyspace_cplx), so <= 4 members of R >= 2 with 4-bit R - 1 fields, and a member's choice d
+// is T.cval[cb + d] (lone match) or the cluster's enumerated choice d (the same format:
+// bytes | len << 56).  The cluster last enumerated stays in the sink's cbuf (res = its
+// ordinal, ~0u: none); build_group enumerates a cluster that is not there again.  A group
+// of two clusters (R1 R2 <= FW_UMAXR: each has <= 8 choices) keeps its first in rows 8..15
+// of the sink's group buffer, whose rows 0..7 are the group descriptors:
+//   off | first unit << 7 (5 bits) | members << 12 (3) | tail << 15 | first entry << 16 (10) |
+//   (R - 1) of members 0..3 << 26 (4 bits each) | piece << 42
+// Only FAST words are built (<= FW_PMAX pieces, <= 255 entries).
+template <class W, class S>
+struct CplxBuilder {
+  const W& wd;
+  const Tab& T;
+  S& sk;
+  const CplxLog& ul;
+  Plan P;             // lconst, minl stay 0
+  u32 bR, bl, bspan;  // the big piece being filled
+  u32 cR, cmax, prev; // cR = 0: no open group
+  u32 nu;             // units taken
+  u32 res;            // the cluster in the sink's cbuf
+  u64 gd;             // the open group's descriptor
+
+  A5X_HD CplxBuilder(const W& w, const Tab& t, S& s, const CplxLog& lg, u32 resident)
+      : wd(w), T(t), sk(s), ul(lg) {
+    P.np = 0; P.ng = 0; P.ne = 0; P.lconst = 0; P.maxl = 0; P.minl = 0; P.ok = true;
+    P.nbig = 0; P.bstarts = 0; P.bent = 0; P.bRp = 0;
+    bR = 1; bl = 0; bspan = 0; cR = 0; cmax = 0; prev = 0; nu = 0; gd = 0; res = resident;
+  }
+  // Planner::big_join (FB_RMAX) for a small piece pi that exists when c (PieceBuilder::big)
+  A5X_HD void big(u32 R, u32 maxlen, u32 pi, bool c) {
+    const bool join = P.nbig && bl + maxlen <= FB_PLEN && bR * R <= FB_RMAX && bspan < FB_SPAN;
+    const bool fresh = c && !join;
+    const u32 nR = join ? bR * R : R;
+    P.bstarts |= fresh && P.nbig >= 1 && P.nbig <= 3 ? (pi & 7u) << ((3u * (P.nbig - 1u)) & 31u) : 0u;
+    P.nbig += fresh ? 1u : 0u;
+    P.bent += c ? (join ? nR - bR : R) : 0u;
+    bR = c ? nR : bR; bl = c ? (join ? bl + maxlen : maxlen) : bl; bspan = c ? (join ? bspan + 1u : 1u) : bspan;
+    const u32 sh = (6u * (P.nbig - 1u)) & 31u;
+    P.bRp = c && P.nbig >= 1 && P.nbig <= FB_NMAX ? (P.bRp & ~(63u << sh)) | (((bR - 1u) & 63u) << sh) : P.bRp;
+  }
+  A5X_HD void literal(u32 off, u32 n, bool nl_last) {  // Planner::literal
+    const u32 nb = nl_last ? n - 1 : n;
+    u64 v = nb ? wd.ld(off, nb) : 0ull;
+    if (nl_last) v |= 10ull << (8 * nb);
+    sk.ent(P.ne, v | fw_meta(n, 1));
+    sk.desc(P.np, fr_desc(1, P.ne));
+    big(1, n, P.np, true);
+    P.ne++; P.np++; P.maxl += n;
+  }
+  A5X_HD void close_group(bool c, bool tail) {
+    if (c) sk.gst(0, P.ng & 7u, gd | ((u64)tail << 15));
+    big(cR, cmax, (u32)(gd >> 42) & 127u, c);
+    P.ne += c ? cR : 0u; P.ng += c ? 1u : 0u; P.maxl += c ? cmax : 0u;
+    cR = c ? 0u : cR;
+  }
+  A5X_HD void unit(const Unit& U) {
+    if (!P.ok) return;
+    const u32 Ru = U.R, ml = U.ml, run = U.s - prev;
+    if (!U.ok || ml > FW_PLEN || Ru > FW_UMAXR || Ru < 2) { P.ok = false; return; }
+    const bool open = cR != 0, merge = open && cmax + run + ml <= FW_PLEN && cR * Ru <= FW_UMAXR;
+    close_group(open && !merge, false);
+    u32 off = prev, rem = run;
+    while (!merge && rem + ml > FW_PLEN) {  // literal run that does not fit with the unit
+      const u32 n = umin32(FW_PLEN, rem);
+      literal(off, n, false);
+      off += n; rem -= n;
+    }
+    const u32 nm = (u32)(gd >> 12) & 7u;  // members of the open group
+    const u64 fresh = (u64)(off & 127u) | ((u64)(nu & 31u) << 7) | (1ull << 12) | ((u64)(P.ne & 1023u) << 16) |
+                      ((u64)(Ru - 1u) << 26) | ((u64)(P.np & 127u) << 42);
+    gd = merge ? (gd + (1ull << 12)) | ((u64)(Ru - 1u) << (26u + 4u * nm)) : fresh;
+    cR = merge ? cR * Ru : Ru;
+    cmax = merge ? cmax + run + ml : rem + ml;
+    P.np += merge ? 0u : 1u;
+    prev = U.e;
+    nu++;
+  }
+  A5X_HD void finish(u32 L) {  // tail bytes + '\n'
+    if (!P.ok) return;
+    const u32 tl = L - prev + 1;
+    const bool open = cR != 0, tm = open && cmax + tl <= FW_PLEN;
+    cmax += tm ? tl : 0u;
+    close_group(open, tm);
+    u32 off = prev, rem = tm ? 0u : tl;
+    while (rem) {
+      const u32 n = umin32(FW_PLEN, rem);
+      literal(off, n, n == rem);
+      off += n; rem -= n;
+    }
+  }
+  // Entries and piece descriptor of group g (< P.ng, < 8): entry a = the lead run, then for each
+  // member its choice d_j and the bytes after it (PieceBuilder::build_group, <= 4 members).
+  A5X_HD void build_group(u32 g, u32 L) {
+    const u64 d = sk.gld(0, g & 7u);
+    const u32 off = (u32)d & 127u, i0 = (u32)(d >> 7) & 31u, nm = (u32)(d >> 12) & 7u;
+    const u32 ebase = (u32)(d >> 16) & 1023u, pi = (u32)(d >> 42) & 127u;
+    const bool tail = (d >> 15) & 1u;
+    const u32 cs = sk.cstride();
+    u64* const cmain = sk.cbuf();
+    u64* const calt = sk.g + 8u * cs;
+    u32 R[4], pl[4];
+    u64 pv[4];
+    const u64* cp[4];
+    u32 cst[4];
+    u32 at = off, ll = 0, ncl = 0;
+    u64 lv = 0;
+    const u64 src = wd.ld(off, umin32(FW_PLEN, L - off));
+    for (u32 j = 0; j < nm && j < 4; j++) ncl += ul.is_cluster(i0 + j) ? 1u : 0u;
+    // the group's clusters into their buffers (a loop of its own, not unrolled: one enumeration
+    // in the code); alt = the first cluster of a group of two
+    u32 seen = 0;
+    for (u32 j = 0; j < nm && j < 4; j++) {
+      const u32 i = i0 + j;
+      if (!ul.is_cluster(i)) continue;
+      const u32 ci = ul.cluster_of(i);
+      const bool alt = ncl > 1 && seen == 0;
+      if (alt || res != ci) {
+        Unit V;
+        ul.get(T, i, V);
+        cluster_enum(wd, V, T, alt ? calt : cmain, cs);
+        if (!alt) res = ci;
+      }
+      seen++;
+    }
+    seen = 0;
+#pragma unroll
+    for (u32 j = 0; j < 4; j++) {
+      R[j] = ((u32)(d >> (26u + 4u * j)) & 15u) + 1u;
+      pl[j] = 0; pv[j] = 0; cp[j] = T.cval; cst[j] = 1;
+      if (j < nm) {
+        const u32 i = i0 + j, e = ul(i), q = e >> 10;
+        u32 end;
+        if (ul.is_cluster(i)) {
+          cp[j] = ncl > 1 && seen == 0 ? calt : cmain; cst[j] = cs;
+          end = q + (e & 1023u);
+          seen++;
+        } else {
+          const A5xKey& key = T.keys[e & 1023u];
+          cp[j] = T.cval + key.choice_base;
+          end = q + key.klen;
+        }
+        const u32 n = q - at;  // the run before the member
+        const u64 v = keep_bytes64(src >> (8 * (at - off)), n);
+        if (j == 0) { lv = v; ll = n; }
+#pragma unroll
+        for (u32 t = 1; t < 4; t++)
+          if (j == t) { pv[t - 1] = v; pl[t - 1] = n; }
+        at = end;
+      }
+    }
+    if (tail) {
+      const u32 n = L - at;
+      const u64 v = keep_bytes64(src >> (8 * (at - off)), n) | (10ull << (8 * n));
+#pragma unroll
+      for (u32 j = 0; j < 4; j++)
+        if (j + 1 == nm) { pv[j] = v; pl[j] = n + 1u; }
+    }
+    const u32 cRg = R[0] * R[1] * R[2] * R[3];
+    u32 dg[4] = {0, 0, 0, 0};
+    for (u32 a = 0; a < cRg; a++) {
+      u64 v = lv;
+      u32 n = ll;
+#pragma unroll
+      for (u32 j = 0; j < 4; j++) {
+        if (j < nm) {
+          const u64 c = cp[j][dg[j] * cst[j]];
+          v |= (c & FW_M56) << (8 * n);
+          n += (u32)(c >> 56);
+          v |= pv[j] << (8 * (n & 7u));
+          n += pl[j];
+        }
+      }
+      sk.ent(ebase + a, (v & FW_M56) | fw_meta(n, cRg));
+      bool carry = true;  // the digits of a + 1, member 0 least significant
+#pragma unroll
+      for (u32 j = 0; j < 4; j++) {
+        dg[j] += carry ? 1u : 0u;
+        carry = dg[j] == R[j];
+        dg[j] = carry ? 0u : dg[j];
+      }
+    }
+    sk.desc(pi, fr_desc(cRg, ebase));
+  }
+};
+
+// One complex word by the lean path: detection, the count pass by unit index (every cluster
+// enumerated once, the last one left in the sink's cbuf), the class (classify_word's), and for
+// a FAST word with candidates and a record slot (fits) its record through sk (sk.np is set
+// here).  Returns why: nonzero = the word is not the lean path's, nothing of C / f is valid and
+// nothing was written.  f = the flags as ks_word_once maps them; built: a record was written
+// (rec0 = its header); bad: the build disagrees with the count pass.
+template <class W, class S>
+A5X_HD u32 cplx_word_lean(const W& wd, u32 L, const Tab& T, int mn, int mx, u32 ringmax, bool fits, S& sk,
+                          WordClass& C, u32& f, bool& built, u64& rec0, bool& bad, CplxLog* keep = nullptr) {
+  built = false; bad = false; rec0 = 0; f = 0;
+  CplxLog lg;
+  if (mx < 1 || L == 0) {  // processWord emits nothing (classify_word)
+    C.count = 0; C.bytes = 0; C.ovf = false; C.clusters = false;
+    C.flags = A5X_WF_RADIX | A5X_WF_FAST;
+    f = C.flags;
+    return L > CL_LMAX ? (u32)CL_WHY_SLOT : 0u;
+  }
+  CplxDetect<W> det(wd, L, T, lg);
+  for (u32 q = 0; q < L; q++) det.at(q);  // (a word past CL_LMAX: the host check's, for its other reasons)
+  det.finish();
+  if (lg.why) return lg.why;
+  CountAcc A;
+  count_init(A, L);
+  CountPlanner<FW_UMAXR> cp;
+  u32 res = ~0u;
+  for (u32 u = 0; u < lg.n; u++) {
+    Unit U;
+    lg.get(T, u, U);
+    if (U.k) {
+#if CL_ABL & 1
+      U.R = 5; U.ml = 2; U.mnl = 1; U.spos = 0; U.sneg = 0; U.maxd = 0;
+#else
+      cluster_enum(wd, U, T, sk.cbuf(), sk.cstride());
+#endif
+      res = lg.cluster_of(u);
+      lg.set_stats(res, U);
+      if (!U.ok) { lg.why |= CL_WHY_CLUSTER; break; }
+    }
+    count_unit(A, U);
+    cp.unit(U);
+  }
+  if (lg.why) return lg.why;
+  cp.finish(L);
+  C = classify_finish(A, cp.P, L, mn, mx, ringmax);
+  f = C.flags;
+  if ((f & A5X_WF_DEFER) || !(f & (A5X_WF_FAST | A5X_WF_RADIX | A5X_WF_ERR_OVF))) f = A5X_WF_DEFER;
+  if (!((f & A5X_WF_FAST) && C.count > 0 && fits)) return 0;
+  sk.np = ff_np(f);
+  CplxBuilder<W, S> pb(wd, T, sk, lg, res);
+  for (u32 u = 0; u < lg.n; u++) {
+    Unit U;
+    lg.get(T, u, U);
+    pb.unit(U);
+  }
+  pb.finish(L);
+  const Plan& P = pb.P;
+  bad = !P.ok || P.ng != ff_ng(f) || P.ne != ff_ne(f) || P.np != ff_np(f) || P.ng > 8u;
+  if (!bad)
+    for (u32 g = 0; g < P.ng; g++) pb.build_group(g, L);
+  rec0 = fr_hdr(P.np, P.ng, P.ne, P.maxl, P.nbig, P.bstarts, P.bRp);
+  built = true;
+  if (keep) *keep = lg;  // (the host check's coverage counters)
+  return 0;
+}
+
+// Host check of the lean path against the generic one (ks_word_once's steps) on one word of
+// <= 127 bytes (a5x_debug_cplx_build, tools/cplx_build_selftest.cpp).  out[0] = 1 when the two
+// agree (flags, count, bytes, the record and its big entries) or the word falls back, out[1] =
+// why (0: the lean path takes the word), out[2] = flags, out[3] = a record was built, out[4..5] =
+// count, out[6..7] = bytes, and of a built record out[8] = units, out[9] = clusters | a group
+// holds two of them << 8, out[10] = groups, out[11] = most members in a group.
+inline void cplx_build_compare(const uint8_t* wd, u32 L, const Tab& T, int mn, int mx, uint32_t* out) {
+  constexpr u32 NREC = 2048;
+  for (int j = 0; j < 12; j++) out[j] = 0;
+  GWord gw;
+  gw.p = wd;
+  // the generic path
+  u64 ra[NREC], rb[NREC];
+  for (u32 i = 0; i < NREC; i++) ra[i] = rb[i] = 0;
+  ArraySink sa, sb;
+  sa.rec = ra; sa.np = 0; sb.rec = rb; sb.np = 0;
+  for (u32 i = 0; i < FW_UMAXR; i++) sa.g[i] = sa.c[i] = sb.g[i] = sb.c[i] = 0;
+  WordClass CA;
+  CA.count = 0; CA.bytes = 0; CA.flags = 0; CA.ovf = false; CA.clusters = false;
+  u32 fa;
+  bool builta = false;
+  u32 benta = 0;
+  if (L > A5X_LMAX_A && mx >= 1) {
+    fa = A5X_WF_DEFER;
+  } else {
+    UnitCache uc;
+    CA = classify_word(gw, L, T, mn, mx, A5X_RING_A - 16, &uc, sa.c, 1);
+    fa = CA.flags;
+    if ((fa & A5X_WF_DEFER) || !(fa & (A5X_WF_FAST | A5X_WF_RADIX | A5X_WF_ERR_OVF))) fa = A5X_WF_DEFER;
+    if ((fa & A5X_WF_FAST) && CA.count > 0) {
+      sa.np = ff_np(fa);
+      const Plan P = uc.full ? plan_word<true>(gw, L, T, sa, fb_balanced_cap(CA.count + 1))
+                             : plan_word_cached(gw, L, T, sa, uc, fb_balanced_cap(CA.count + 1));
+      ra[0] = fr_hdr(P.np, P.ng, P.ne, P.maxl, P.nbig, P.bstarts, P.bRp);
+      benta = P.bent;
+      builta = true;
+    }
+  }
+  // the lean path (a second group buffer: rows 8..15 take a cluster)
+  WordClass CB;
+  CB.count = 0; CB.bytes = 0; CB.flags = 0; CB.ovf = false; CB.clusters = false;
+  u32 fb = 0;
+  bool builtb = false, bad = false;
+  u64 rec0 = 0;
+  CplxLog lg;
+  const u32 why = cplx_word_lean(gw, L, T, mn, mx, A5X_RING_A - 16, true, sb, CB, fb, builtb, rec0, bad, &lg);
+  out[1] = why;
+  if (why) {
+    out[0] = 1; out[2] = fa; out[3] = builta ? 1u : 0u;
+    out[4] = (u32)CA.count; out[5] = (u32)(CA.count >> 32); out[6] = (u32)CA.bytes; out[7] = (u32)(CA.bytes >> 32);
+    return;
+  }
+  rb[0] = rec0;
+  const bool defer = (fb & A5X_WF_DEFER) != 0;  // (the kernel stores count = bytes = 0 for a deferred word)
+  bool eq = fa == fb && builta == builtb && !bad && (defer || (CA.count == CB.count && CA.bytes == CB.bytes)) &&
+            CA.ovf == CB.ovf;
+  if (!defer && (fb & A5X_WF_FAST) && CB.count > 0) eq = eq && CA.clusters == CB.clusters;
+  for (u32 i = 0; i < NREC; i++) eq = eq && ra[i] == rb[i];
+  out[0] = eq ? 1u : 0u;
+  out[2] = fb; out[3] = builtb ? 1u : 0u;
+  out[4] = (u32)CB.count; out[5] = (u32)(CB.count >> 32); out[6] = (u32)CB.bytes; out[7] = (u32)(CB.bytes >> 32);
+  (void)benta;
+  if (builtb) {
+    out[8] = lg.n; out[9] = lg.nc; out[10] = frh_ng(rb[0]);
+    for (u32 g = 0; g < frh_ng(rb[0]) && g < 8u; g++) {
+      const u32 i0 = (u32)(sb.g[g] >> 7) & 31u, nm = (u32)(sb.g[g] >> 12) & 7u;
+      out[11] = umax32(out[11], nm);
+      u32 ncl = 0;
+      for (u32 j = 0; j < nm; j++) ncl += lg.is_cluster(i0 + j) ? 1u : 0u;
+      if (ncl > 1) out[9] |= 256u;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // k_expand_fast, per candidate (host replay in a5x_debug_plan_word)
 // ---------------------------------------------------------------------------
 // pass 1 over the window records wrec: word with its np piece descriptors at

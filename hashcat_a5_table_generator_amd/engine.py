@@ -524,6 +524,13 @@ class Context:
         self._chk(self._L.a5x_debug_keyspace_refit(self.h, ctypes.byref(n)))
         return n.value
 
+    def keyspace_cplx_lean(self) -> Tuple[int, int]:
+        """(lean, generic): the words of the last keyspace pass that ``k_keyspace_cplx`` took by
+        its lean path and by its generic unit walk (``a5x_debug_keyspace_cplx_lean``; a test hook)."""
+        n = (ctypes.c_uint64 * 2)()
+        self._chk(self._L.a5x_debug_keyspace_cplx_lean(self.h, n))
+        return n[0], n[1]
+
     def keyspace_small_stage(self) -> int:
         """The small word stage of ``k_keyspace_thread`` for the loaded table in bytes, 0 when
         the table leaves no room for one (``a5x_debug_keyspace_small_stage``; a test hook)."""

@@ -455,6 +455,27 @@ A5X_API int a5x_debug_piece_build(a5x_ctx* ctx, const uint8_t* word, size_t len,
  * index.  Synchronises the device.  Never called by a compute path. */
 A5X_API int a5x_debug_keyspace_refit(a5x_ctx* ctx, uint64_t* out);
 
+/* Test hook (CPU test suite): ONE complex word (<= 127 bytes) by the two paths of
+ * k_keyspace_cplx, the lean one (matches by the compact key records, units by index, a
+ * record built per piece, clusters included) and the generic unit walk, on the host over
+ * the same code.  out[12]: out[0] = 1 the two agree in flags, count, bytes and every u64 of
+ * the record (or the word is not the lean path's), 0 they differ; out[1] = why the word is
+ * left to the generic path, 0 when the lean path takes it: 1 a key longer than 4 bytes,
+ * 2 more than 16 units, 4 a unit at byte >= 64, 8 a key index >= 1024, 16 a cluster of
+ * more than 8 matches, more than 16 choices or a choice longer than 7 bytes, 32 more than
+ * 2 clusters, 64 a word longer than the kernel's 36-byte word slot (a sum of these; the
+ * cluster test runs only when nothing else is set); out[2] = flags, out[3] = a record was
+ * built, out[4..5] = count, out[6..7] = bytes, and of a built record out[8] = units, out[9] =
+ * clusters | 256 when one group holds two of them, out[10] = group pieces, out[11] = most
+ * units in one group. */
+A5X_API int a5x_debug_cplx_build(a5x_ctx* ctx, const uint8_t* word, size_t len, int min_sub, int max_sub,
+                                 uint32_t* out);
+
+/* Test hook (GPU test suite): out[2] = the words of the context's last keyspace pass that
+ * k_keyspace_cplx took by its lean path and by its generic path.  Synchronises the device.
+ * Never called by a compute path. */
+A5X_API int a5x_debug_keyspace_cplx_lean(a5x_ctx* ctx, uint64_t* out);
+
 /* Test hooks: the word stage of k_keyspace_thread, the LDS bytes that hold a tile's words.
  * The byte walk has two: the large one (8192 B, four workgroups per CU) and a small one sized
  * to the loaded table so that the workgroup takes <= 32,000 B of LDS (25 allocation granules
