@@ -40,6 +40,8 @@ EXPORTS = (
     "a5x_set_salted_targets", "a5x_load_salted_hashes", "a5x_salt_count", "a5x_salt_get", "a5x_hit_salts",
     "a5x_salts_last", "a5x_format_hits_salted", "a5x_digest_lines_salted_device", "a5x_debug_digest_salted",
     "a5x_algo_salt_order",
+    "a5x_set_iterated_targets", "a5x_load_pbkdf2_hashes", "a5x_salt_iterations", "a5x_format_hits_iterated",
+    "a5x_debug_pbkdf2", "a5x_debug_iter_budget",
     "a5x_debug_target_set",
 )
 
@@ -165,6 +167,13 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     L.a5x_format_hits_salted.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, i, SINK, vp]
     L.a5x_digest_lines_salted_device.argtypes = [vp, i, i, vp, u64, vp, u64, ctypes.POINTER(u64), vp]
     L.a5x_debug_digest_salted.argtypes = [i, i, ctypes.c_char_p, sz, ctypes.c_char_p, sz, vp, sz]
+    L.a5x_set_iterated_targets.argtypes = [vp, i, vp, u64, vp, vp, vp]
+    L.a5x_load_pbkdf2_hashes.argtypes = [vp, i, ctypes.c_char_p, sz, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                         ctypes.POINTER(u64)]
+    L.a5x_salt_iterations.argtypes = [vp, u32, ctypes.POINTER(u32)]
+    L.a5x_format_hits_iterated.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, ctypes.POINTER(u64), SINK, vp]
+    L.a5x_debug_pbkdf2.argtypes = [i, ctypes.c_char_p, sz, ctypes.c_char_p, sz, u32, vp, sz]
+    L.a5x_debug_iter_budget.argtypes = [vp, u64, u64, ctypes.POINTER(u64)]
     L.a5x_debug_target_set.argtypes = [u32, vp, u64, vp, vp, sz, vp, sz, vp, sz, vp, sz]
     _lib = L
     return L

@@ -20,9 +20,10 @@ CLI = os.path.join(OUT, "a5x_generator")
 ARCH = os.environ.get("A5X_OFFLOAD_ARCH", "gfx950")
 
 LIB_SRCS = ["a5x_kernels.hip", "a5x_modes.hip", "a5x_digest.hip", "a5x_digest_nest.hip", "a5x_rules.hip", "a5x_rules_wide.hip",
-            "a5x_rules_nest.hip", "a5x_salt.hip", "a5x_salt_nest.hip", "a5x_hmac.hip", "a5x_host.cpp"]
+            "a5x_rules_nest.hip", "a5x_salt.hip", "a5x_salt_nest.hip", "a5x_hmac.hip", "a5x_pbkdf2.hip",
+            "a5x_host.cpp"]
 HEADERS = ["a5x_format.h", "a5x_gosem.h", "a5x_launch.h", "a5x_plan.h", "a5x_fx6.h", "a5x_ring.h", "a5x_md.h", "a5x_sha.h", "a5x_rules.h",
-           "a5x_salt.h", "a5x_nest.h", "a5x_stream.h", "a5x_salt_nest.h", "a5x_hmac.h"]
+           "a5x_salt.h", "a5x_nest.h", "a5x_stream.h", "a5x_salt_nest.h", "a5x_hmac.h", "a5x_pbkdf2.h"]
 
 
 def _hipcc() -> str:

@@ -10,7 +10,8 @@
 //                                          md5-md5up|md5-sha1|sha1-sha1|sha1-md5|sha256-md5|
 //                                          md5-md5.salt|md5-salt.md5|md5-md5.md5salt|md5-md5salt.md5|
 //                                          sha1-sha1.salt|sha1-salt.sha1|sha1-md5.salt|
-//                                          hmac-{md5,sha1,sha256,sha512}-key-{pass,salt}] [--rules <file>]
+//                                          hmac-{md5,sha1,sha256,sha512}-key-{pass,salt}|
+//                                          pbkdf2-hmac-{md5,sha1,sha256,sha512}] [--rules <file>]
 //                                  [--salted=pass.salt|salt.pass [--hex-salt]]]
 //                 [--skip N] [--limit N] [--keyspace]
 //
@@ -36,6 +37,13 @@
 // So are the HMAC algorithms, hmac-HASH-key-pass (the candidate is the key, the salt the message:
 // hashcat -m 50 / 150 / 1450 / 1750 for md5 / sha1 / sha256 / sha512, order pass.salt) and
 // hmac-HASH-key-salt (the salt is the key: -m 60 / 160 / 1460 / 1760, order salt.pass).
+//
+// The PBKDF2 algorithms pbkdf2-hmac-md5 / -sha1 / -sha256 / -sha512 (hashcat -m 11900 / 12000 /
+// 10900 / 12100) are iterated lists: <file> holds hashcat's "name:iterations:base64(salt):
+// base64(key)" lines, the output is "original-line:plain".  A target matches on the first 16
+// bytes of its key on the GPU; before a hit is printed the whole key is derived again on the host,
+// and a hit that fails there is dropped and counted on stderr.  --salted, --hex-salt and --rules
+// do not apply to them.
 //
 // --skip / --limit / --keyspace (a5x extension, SURVEY §5 checkpoint / resume): the
 // stream's candidate order does not depend on batching (a word's candidates are
@@ -97,7 +105,11 @@ static void usage(FILE* f) {
           "                                    hmac-sha256-key-pass (-m 1450), hmac-sha512-key-pass (-m 1750),\n"
           "                                    or the salt as the key: hmac-md5-key-salt (-m 60),\n"
           "                                    hmac-sha1-key-salt (-m 160), hmac-sha256-key-salt (-m 1460),\n"
-          "                                    hmac-sha512-key-salt (-m 1760)\n"
+          "                                    hmac-sha512-key-salt (-m 1760);\n"
+          "                                    PBKDF2 (FILE holds name:iterations:base64(salt):base64(key)\n"
+          "                                    lines, the output is line:plain): pbkdf2-hmac-md5 (-m 11900),\n"
+          "                                    pbkdf2-hmac-sha1 (-m 12000), pbkdf2-hmac-sha256 (-m 10900),\n"
+          "                                    pbkdf2-hmac-sha512 (-m 12100); not with --salted, --hex-salt, --rules\n"
           "      --salted=ORDER                With --hashes: FILE holds hash:salt lines; ORDER is pass.salt\n"
           "                                    (hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710) or salt.pass\n"
           "                                    (-m 20 / 120 / 1320 / 1420 / 10820 / 1720); --algo also takes\n"
@@ -273,6 +285,31 @@ static int load_salted_targets(a5x_ctx* ctx, const char* path, int algo, int ord
   return rc;
 }
 
+// a PBKDF2 --algo: the whole "name:iterations:base64(salt):base64(key)" file through a5x_load_pbkdf2_hashes
+static int load_pbkdf2_targets(a5x_ctx* ctx, const char* path, int algo) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return A5X_E_IO;
+  std::vector<uint8_t> text;
+  uint8_t buf[1 << 16];
+  size_t n;
+  while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.insert(text.end(), buf, buf + n);
+  const bool bad = ferror(f) != 0;
+  fclose(f);
+  if (bad) return A5X_E_IO;
+  uint64_t nt = 0, ns = 0, nsk = 0;
+  const int rc = a5x_load_pbkdf2_hashes(ctx, algo, text.data(), text.size(), &nt, &ns, &nsk);
+  if (rc == 0)
+    fprintf(stderr, "a5_generator: iterated: %llu target(s), %llu distinct (salt, iterations) pair(s), %llu line(s) skipped "
+                    "(not name:iterations:base64:base64 of this algorithm)\n",
+            (unsigned long long)nt, (unsigned long long)ns, (unsigned long long)nsk);
+  return rc;
+}
+
+static int sink_string(void* user, const uint8_t* p, size_t n) {
+  ((std::string*)user)->append((const char*)p, n);
+  return 0;
+}
+
 static bool parse_u64(const char* s, uint64_t* out) {
   char* e;
   errno = 0;
@@ -438,15 +475,21 @@ int main(int argc, char** argv) {
       else if (v == "hmac-sha256-key-salt" || v == "1460") algo = A5X_ALGO_HMAC_SHA256_KEY_SALT;
       else if (v == "hmac-sha512-key-pass" || v == "1750") algo = A5X_ALGO_HMAC_SHA512_KEY_PASS;
       else if (v == "hmac-sha512-key-salt" || v == "1760") algo = A5X_ALGO_HMAC_SHA512_KEY_SALT;
+      else if (v == "pbkdf2-hmac-md5" || v == "11900") algo = A5X_ALGO_PBKDF2_HMAC_MD5;
+      else if (v == "pbkdf2-hmac-sha1" || v == "12000") algo = A5X_ALGO_PBKDF2_HMAC_SHA1;
+      else if (v == "pbkdf2-hmac-sha256" || v == "10900") algo = A5X_ALGO_PBKDF2_HMAC_SHA256;
+      else if (v == "pbkdf2-hmac-sha512" || v == "12100") algo = A5X_ALGO_PBKDF2_HMAC_SHA512;
       else {
         fprintf(stderr, "a5_generator: error: --algo: md5, ntlm, sha1, sha224, sha256, sha384 or sha512, or nested:\n"
                         "md5-md5, md5-md5-md5, md5-md5up, md5-sha1, sha1-sha1, sha1-md5 or sha256-md5, or salted nested:\n"
                         "md5-md5.salt, md5-salt.md5, md5-md5.md5salt, md5-md5salt.md5, sha1-sha1.salt, sha1-salt.sha1\n"
                         "or sha1-md5.salt, or HMAC: hmac-md5-key-pass, hmac-md5-key-salt, hmac-sha1-key-pass, hmac-sha1-key-salt,\n"
-                        "hmac-sha256-key-pass, hmac-sha256-key-salt, hmac-sha512-key-pass or hmac-sha512-key-salt\n");
+                        "hmac-sha256-key-pass, hmac-sha256-key-salt, hmac-sha512-key-pass or hmac-sha512-key-salt, or PBKDF2:\n"
+                        "pbkdf2-hmac-md5, pbkdf2-hmac-sha1, pbkdf2-hmac-sha256 or pbkdf2-hmac-sha512\n");
         return 80;
       }
       // (a salted nested or HMAC algorithm implies a salted list in its own order, as a salted mode number does)
+      // (so does a PBKDF2 algorithm: order 0, its hits carry the index of their (salt, iterations) pair)
       if (a5x_algo_salt_order(algo) >= 0) mode_order = a5x_algo_salt_order(algo);
     } else if (s.rfind("--salted", 0) == 0) {
       salted = val_of("--salted");
@@ -493,6 +536,16 @@ int main(int argc, char** argv) {
   setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
   if (!rules.empty() && hashes.empty()) {
     fprintf(stderr, "a5_generator: error: --rules applies to the digest + lookup stage: it needs --hashes\n");
+    return 80;
+  }
+  const bool iterated = algo >= A5X_ALGO_PBKDF2_HMAC_MD5 && algo <= A5X_ALGO_PBKDF2_HMAC_SHA512;
+  if (iterated && (!salted.empty() || hex_salt)) {
+    fprintf(stderr, "a5_generator: error: --salted / --hex-salt with a PBKDF2 --algo: its list holds\n"
+                    "name:iterations:base64(salt):base64(key) lines, the salt is part of each line and always base64\n");
+    return 80;
+  }
+  if (iterated && !rules.empty()) {
+    fprintf(stderr, "a5_generator: error: --rules with a PBKDF2 --algo: rules and iterated lists together are not supported\n");
     return 80;
   }
   int order = -1;  // >= 0: the --hashes list is salted
@@ -658,7 +711,8 @@ int main(int argc, char** argv) {
   }
   FILE* f = fopen(dict.c_str(), "rb");
   if (!f) { perror(dict.c_str()); a5x_destroy(ctx); return 1; }
-  if ((rc = order >= 0 ? load_salted_targets(ctx, hashes.c_str(), algo, order, hex_salt) : load_targets(ctx, hashes.c_str(), algo))) {
+  if ((rc = iterated ? load_pbkdf2_targets(ctx, hashes.c_str(), algo)
+            : order >= 0 ? load_salted_targets(ctx, hashes.c_str(), algo, order, hex_salt) : load_targets(ctx, hashes.c_str(), algo))) {
     fprintf(stderr, "a5_generator: %s\n", rc == A5X_E_IO ? "cannot read --hashes file" : a5x_last_error(ctx));
     a5x_destroy(ctx);
     fclose(f);
@@ -683,7 +737,7 @@ int main(int argc, char** argv) {
   }
   const bool ruled = !rules.empty();
   const bool with_salts = order >= 0;
-  uint64_t skipped_pairs = 0;
+  uint64_t skipped_pairs = 0, dropped_hits = 0;
   DictStream ds(f, chunk);
   std::vector<uint8_t> words;
   std::vector<uint64_t> sub;
@@ -727,13 +781,28 @@ int main(int argc, char** argv) {
       if ((rc = a5x_hit_digest(ctx, &hits[h], full, sizeof full, &fl))) break;
       std::string key((const char*)full, fl);
       if (with_salts) key.append((const char*)&hrule[h], 4);  // a target is a (hash, salt) pair
-      if (cracked.insert(key).second) {
+      // (an iterated list: a hit on 16 bytes may still be dropped, so every hit goes to the check
+      // below and the lines that come out of it are deduplicated)
+      if (iterated || cracked.insert(key).second) {
         first.push_back(hits[h]);
         first_rule.push_back(hrule[h]);
       }
     }
     if (rc) break;
-    if (with_salts)
+    if (iterated) {
+      std::string text;
+      uint64_t drop = 0;
+      rc = a5x_format_hits_iterated(ctx, wb, sub.data(), nb, mode, tmin, tmax, first.data(), first.size(), first_rule.data(),
+                                    &drop, sink_string, &text);
+      dropped_hits += drop;
+      for (size_t p0 = 0; rc == 0 && p0 < text.size();) {
+        const size_t e = text.find('\n', p0);
+        size_t k = p0;  // the target: the list's line, which has three ':' (base64 has none)
+        for (int colons = 0; k < e && colons < 4; k++) colons += text[k] == ':';
+        if (cracked.insert(text.substr(p0, k - p0)).second) fwrite(text.data() + p0, 1, e + 1 - p0, stdout);
+        p0 = e + 1;
+      }
+    } else if (with_salts)
       rc = a5x_format_hits_salted(ctx, wb, sub.data(), nb, mode, tmin, tmax, first.data(), first.size(),
                                   first_rule.data(), hex_salt ? 1 : 0, sink_stdout, nullptr);
     else if (ruled)
@@ -749,6 +818,9 @@ int main(int argc, char** argv) {
   if (with_salts)
     fprintf(stderr, "a5_generator: salted: %llu (candidate, salt) pair(s) longer than 128 bytes skipped\n",
             (unsigned long long)skipped_pairs);
+  if (iterated)
+    fprintf(stderr, "a5_generator: iterated: %llu hit(s) on the first 16 bytes dropped (the rest of the key differs)\n",
+            (unsigned long long)dropped_hits);
   fclose(f);
   fflush(stdout);
   if (rc) fprintf(stderr, "a5_generator: %s\n", a5x_last_error(ctx));

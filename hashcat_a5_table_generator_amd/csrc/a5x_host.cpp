@@ -34,6 +34,7 @@
 #include "a5x_rules.h"
 #include "a5x_salt.h"
 #include "a5x_hmac.h"
+#include "a5x_pbkdf2.h"
 #include "a5x_salt_nest.h"
 #include "a5x_sha.h"
 
@@ -207,6 +208,17 @@ struct a5x_ctx {
   DevBuf<uint32_t> s_table, dg_hit_salt;
   std::vector<uint32_t> s_hit_salt;
   uint64_t s_hashed = 0, s_skipped = 0;
+  // iterated target lists (a5x_pbkdf2.hip): a salted set of order 0 whose "salts" are distinct
+  // (salt, iterations) pairs -- the count of each, per target its index, the whole key the list
+  // gave and its line (a5x_load_pbkdf2_hashes; empty: none), the targets of each (index, first 16
+  // bytes).  The pairs' state buffer; the budgets of a pass and of a loop launch (0: the defaults,
+  // a5x_debug_iter_budget) and the latest call's loop launches.
+  std::vector<uint32_t> it_iters, it_tidx;
+  std::vector<std::vector<uint8_t>> it_keys;
+  std::vector<std::string> it_lines;
+  std::map<std::pair<uint32_t, std::array<uint8_t, 16>>, std::vector<uint64_t>> it_by_key;
+  DevBuf<uint32_t> it_state;
+  uint64_t it_slots = 0, it_pair_iters = 0, it_launches = 0;
 
   DevBuf<uint64_t> count, bytes, cand_off, byte_off, scan_tmp, locate;
   DevBuf<uint32_t> flags, defer, chunk_w0, slow_list, big_list, roff, cplx;
@@ -1327,17 +1339,21 @@ inline uint32_t algo_size(int algo) { return 4u * a5x_algo_words(algo); }  // (4
 // no salted mode: NTLM and the nested algorithms
 inline bool algo_unsalted(int algo) { return algo == A5X_ALGO_NTLM || a5x_algo_nested(algo); }
 // the salted nested algorithms 32..38 (a5x_salt_nest.h) and the HMAC algorithms 48..55 (a5x_hmac.h):
-// salted sets only, each with its own salt order and its own salt records
-inline bool algo_salted_only(int algo) { return a5x_algo_salt_nested(algo) || a5x_algo_hmac(algo); }
+// salted sets only, each with its own salt order and its own salt records; the PBKDF2 algorithms
+// 72..75 (a5x_pbkdf2.h) likewise, as iterated sets (a5x_set_iterated_targets), order 0
+inline bool algo_salted_only(int algo) { return a5x_algo_salt_nested(algo) || a5x_algo_hmac(algo) || a5x_algo_pbkdf2(algo); }
 // that order (a5x_algo_salt_order); -1: not such an algorithm
-inline int salted_only_order(int algo) { return a5x_algo_hmac(algo) ? hmac_order(algo) : snest_order(algo); }
+inline int salted_only_order(int algo) {
+  return a5x_algo_pbkdf2(algo) ? A5X_SALT_ORDER_PASS_SALT : a5x_algo_hmac(algo) ? hmac_order(algo) : snest_order(algo);
+}
 // u32 per record of a salted set's device salt table, by the set's kind
 inline uint32_t salt_stride(int algo) {
   return a5x_algo_hmac(algo) ? A5X_HMAC_STRIDE : a5x_algo_salt_nested(algo) ? A5X_SNEST_STRIDE : A5X_SALT_STRIDE;
 }
 // the stream kernel of a salted set, by the algorithm its salt records were built for
 inline hipError_t launch_salted(int rec_algo, const A5xSaltLaunch& SL, int op, uint32_t cus, hipStream_t st) {
-  return a5x_algo_hmac(rec_algo) ? a5x_launch_hmac_stream(SL, op, cus, st)
+  return a5x_algo_pbkdf2(rec_algo) ? hipErrorInvalidValue  // (an iterated set has no stream kernel: iter_stream)
+       : a5x_algo_hmac(rec_algo) ? a5x_launch_hmac_stream(SL, op, cus, st)
        : a5x_algo_salt_nested(rec_algo) ? a5x_launch_salt_nest_stream(SL, op, cus, st)
                                         : a5x_launch_salt_stream(SL, op, cus, st);
 }
@@ -1824,6 +1840,64 @@ int digest_fused_default(a5x_ctx* c, const Job& J, const DigestCall& Q) {
   return digest_finish(c, Q, nh, total);
 }
 
+
+// ---- iterated sets (a5x_pbkdf2.hip) --------------------------------------------------------
+// The defaults of a pass and of a loop launch.  IT_SLOTS pair slots: at 55 state words a pair
+// (SHA-512) 220 MiB of state, and more than five rounds of the 196608 lanes the device holds.
+// IT_PAIR_ITERS pair-iterations bound the time of one loop launch (DESIGN "Iterated target
+// lists" has the measured times).
+constexpr uint64_t IT_SLOTS = 1ull << 20;
+constexpr uint64_t IT_PAIR_ITERS = 1ull << 30;
+
+// The passes of a stream whose line starts are counted and scanned (L.s.d.blk_pre = dg_blk_pre,
+// nblk + 1 entries): blocks are taken while their lines, rounded up to a wave, fit the pass's
+// slots under every salt record; a run of blocks that does not -- at the least one block, so a
+// pass may exceed a budget smaller than a block's lines under one record -- is taken under a
+// slice of the records at a time.  Per pass: init, the loop launches of at most slice =
+// max(1, B / pairs) iterations up to the largest count of the pass's records, then per_pass(L)
+// (the compare step, as often as it likes: the iterations never run again).
+template <class PerPass>
+int iter_stream(a5x_ctx* c, A5xPbkdf2Launch& L, uint64_t nblk, hipStream_t st, PerPass per_pass) {
+  int rc;
+  const uint32_t S = c->n_salts, sw = pbkdf2_state_words(c->t_algo);
+  const uint64_t P = c->it_slots ? c->it_slots : IT_SLOTS, B = c->it_pair_iters ? c->it_pair_iters : IT_PAIR_ITERS;
+  const uint32_t cus = (uint32_t)std::max(1, c->cus);
+  std::vector<uint64_t> pre(nblk + 1);
+  HIPCHK(c, hipMemcpyAsync(pre.data(), c->dg_blk_pre.p, (nblk + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  auto slots = [](uint64_t lines) { return (lines + 63) & ~63ull; };
+  for (uint64_t b0 = 0; b0 < nblk;) {
+    uint64_t b1 = b0 + 1;
+    while (b1 < nblk && slots(pre[b1 + 1] - pre[b0]) * S <= P) b1++;
+    const uint64_t lines = pre[b1] - pre[b0];
+    if (lines > 0xffffffc0ull) return fail(c, A5X_E_UNSUPPORTED, "more lines in a pass than slots can be numbered");
+    const uint32_t np = (uint32_t)slots(lines);
+    const uint32_t ns = np ? (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(1, P / np)) : S;
+    for (uint32_t s0 = 0; lines && s0 < S; s0 += ns) {
+      L.b0 = b0; L.b1 = b1; L.np = np;
+      L.s0 = s0; L.s1 = std::min(S, s0 + ns);
+      L.pairs = (uint64_t)(L.s1 - L.s0) * np;
+      if ((rc = grow(c, c->it_state, L.pairs * sw))) return rc;
+      L.state = c->it_state.p;
+      HIPCHK(c, hipMemsetAsync(L.state + L.pairs, 0xff, L.pairs * 4, st));  // word 1 of every slot: no pair yet
+      HIPCHK(c, a5x_launch_pbkdf2_init(L, 0, cus, st));
+      uint32_t cmax = 1;
+      for (uint32_t k = L.s0; k < L.s1; k++)
+        cmax = std::max(cmax, c->s_recs[(size_t)k * A5X_PBKDF2_STRIDE + A5X_PBKDF2_R_ITERS]);
+      const uint64_t slice = std::max<uint64_t>(1, B / L.pairs);
+      for (uint64_t k0 = 1; k0 < cmax; k0 += slice) {
+        L.k0 = (uint32_t)k0;
+        L.k1 = (uint32_t)std::min<uint64_t>(cmax, k0 + slice);
+        HIPCHK(c, a5x_launch_pbkdf2_loop(L, st));
+        c->it_launches++;
+      }
+      if ((rc = per_pass(L))) return rc;
+    }
+    b0 = b1;
+  }
+  return A5X_OK;
+}
+
 // Two-pass route, the range loop: each range of at most scratch_bytes is expanded into HBM
 // scratch (job_launch), then a stream kernel hashes its lines -- k_digest_stream, with rules
 // k_rules_stream, with a salted set k_salt_stream.  Hits are (block, ordinal) until
@@ -1833,6 +1907,7 @@ int digest_fused_default(a5x_ctx* c, const Job& J, const DigestCall& Q) {
 int digest_two_pass(a5x_ctx* c, const Job& J, const DigestCall& Q) {
   int rc;
   const bool wide = c->t_tw != 0, ruled = c->n_rules != 0, salted = c->salted;
+  const bool iterated = salted && a5x_algo_pbkdf2(c->t_algo);  // passes of pairs instead of one stream launch
   const uint64_t nw = J.nw, hit_cap = Q.hit_cap;
   a5x_hit* const hits = Q.hits;
   uint64_t cap = Q.scratch_bytes ? Q.scratch_bytes : ((uint64_t)2 << 30);
@@ -1850,7 +1925,9 @@ int digest_two_pass(a5x_ctx* c, const Job& J, const DigestCall& Q) {
   H.tail_words = wide ? HT : 0;
   H.side = side;
   H.flags_full = true;
-  if ((rc = hits_open(c, H, hit_cap))) return rc;
+  // (an iterated set: a pass's hits are few against its work and a second run costs only the
+  // compare step, so its buffer starts at the floor whatever the caller's)
+  if ((rc = iterated ? hits_resize(c, H, 1024) : hits_open(c, H, hit_cap))) return rc;
   if (side && (rc = grow(c, c->r_counter, 2))) return rc;
   auto launch_op0 = [&](const A5xDigLaunch& D) -> hipError_t {
     const uint32_t cus = (uint32_t)std::max(1, c->cus);
@@ -1909,19 +1986,10 @@ int digest_two_pass(a5x_ctx* c, const Job& J, const DigestCall& Q) {
       ms_dig += md;
       return decode_dev_err(c, c->h_scalars[S_ERR] & ~(1u << 10));  // (STREAM_ERR_HITCAP is hits_run's business)
     };
-    if ((rc = hits_run(c, J.st, H, &nh, digest, [&](uint64_t n) { return copied >= hit_cap ? 0 : n; }))) return rc;
-    if (salted) {
-      const uint64_t pairs = (R.ce - R.cb) * c->n_salts;
-      if (rej > pairs) return fail(c, A5X_E_HIP, "more skipped pairs than the range has");
-      c->s_skipped += rej;
-      c->s_hashed += pairs - rej;
-    }
-    if (ruled) {
-      if (rej > R.ce - R.cb) return fail(c, A5X_E_HIP, "more rejected lines than the range has candidates");
-      c->r_rejected += rej;
-      c->r_hashed += (R.ce - R.cb - rej) * c->n_rules;
-    }
-    if (nh) {
+    // the hits of one hits_run out of the device buffer: resolved to (word, candidate) and copied
+    // to the caller behind those already there
+    auto deliver = [&]() -> int {
+      if (!nh) return A5X_OK;
       const uint64_t got = std::min<uint64_t>(nh, H.n);
       HIPCHK(c, a5x_launch_scan(c->dg_blk_cnt.p, c->dg_blk_cnt.p, nblk, c->dg_blk_pre.p, c->dg_blk_pre.p,
                                 c->scan_tmp.p, c->d_scalars + S_ERR, J.st));
@@ -1947,7 +2015,62 @@ int digest_two_pass(a5x_ctx* c, const Job& J, const DigestCall& Q) {
         }
       copied += take;
       found += nh;
+      return A5X_OK;
+    };
+    if (iterated && c->n_salts) {
+      // An iterated set: the range's line starts first (every pass needs the blocks' ordinals),
+      // then pass by pass init, the loop launches and the compare step.  Each pass's hits are
+      // taken out of the one hit buffer before the next pass's go in; when the buffer was too
+      // small, hits_run repeats the compare step alone.
+      A5xPbkdf2Launch L;
+      memset(&L, 0, sizeof L);
+      L.s = {D, c->s_table.p, c->n_salts, c->s_order, side->p, c->r_counter.p};
+      HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, J.st));
+      auto op1 = [&] {
+        L.b0 = 0; L.b1 = nblk;
+        return a5x_launch_pbkdf2_init(L, 1, (uint32_t)std::max(1, c->cus), J.st);
+      };
+      if ((rc = stream_count_lines(c, op1, nblk, J.st, nullptr))) return rc;
+      L.s.d.blk_pre = c->dg_blk_pre.p;
+      HIPCHK(c, hipEventRecord(c->dev_ev[0], J.st));
+      rc = iter_stream(c, L, nblk, J.st, [&](A5xPbkdf2Launch& Lp) -> int {
+        int rc2;
+        auto compare = [&]() -> int {
+          Lp.s.d.hits = c->dg_hits.p;
+          Lp.s.d.hit_cap = (uint32_t)H.n;
+          Lp.s.d.nhits = c->d_scalars + S_NHITS;
+          Lp.s.hit_salt = side->p;
+          HIPCHK(c, a5x_launch_pbkdf2_compare(Lp, 0, J.st));
+          HIPCHK(c, read_scalars(c, J.st, S_NHITS));
+          HIPCHK(c, hipStreamSynchronize(J.st));
+          return decode_dev_err(c, c->h_scalars[S_ERR] & ~(1u << 10));
+        };
+        if ((rc2 = hits_run(c, J.st, H, &nh, compare, [&](uint64_t n) { return copied >= hit_cap ? 0 : n; }))) return rc2;
+        return deliver();
+      });
+      if (rc) return rc;
+      HIPCHK(c, hipEventRecord(c->dev_ev[1], J.st));
+      HIPCHK(c, hipMemcpyAsync(&rej, c->r_counter.p, 8, hipMemcpyDeviceToHost, J.st));
+      HIPCHK(c, hipStreamSynchronize(J.st));
+      float md = 0;
+      HIPCHK(c, hipEventElapsedTime(&md, c->dev_ev[0], c->dev_ev[1]));
+      ms_dig += md;
+      nh = 0;  // (delivered pass by pass)
+    } else if ((rc = hits_run(c, J.st, H, &nh, digest, [&](uint64_t n) { return copied >= hit_cap ? 0 : n; }))) {
+      return rc;
     }
+    if (salted) {
+      const uint64_t pairs = (R.ce - R.cb) * c->n_salts;
+      if (rej > pairs) return fail(c, A5X_E_HIP, "more skipped pairs than the range has");
+      c->s_skipped += rej;
+      c->s_hashed += pairs - rej;
+    }
+    if (ruled) {
+      if (rej > R.ce - R.cb) return fail(c, A5X_E_HIP, "more rejected lines than the range has candidates");
+      c->r_rejected += rej;
+      c->r_hashed += (R.ce - R.cb - rej) * c->n_rules;
+    }
+    if ((rc = deliver())) return rc;
     total.expand_launches += 1;
   }
   total.ms_keyspace = ms_ks;
@@ -1972,6 +2095,7 @@ int expand_digest(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, ui
   c->r_rejected = c->r_hashed = 0;
   c->s_hit_salt.clear();
   c->s_hashed = c->s_skipped = 0;
+  c->it_launches = 0;
   // The fused kernels hash plain MD5 and NTLM only.  The two-pass range loop in every mode for:
   // a wide set (SHA-1 and the SHA-2 family); a nested one (a5x_nest.h -- an MD5-outer one is not
   // wide, and the fused kernels would hash it as plain MD5); rules loaded (k_rules_stream); a
@@ -2098,7 +2222,7 @@ void a5x_destroy(a5x_ctx* c) {
   release(c->dg_cand_off); release(c->dg_byte_off); release(c->dg_hits);
   release(c->t_tails); release(c->t_ztails); release(c->dg_hit_tail);
   release(c->r_table); release(c->dg_hit_rule); release(c->r_counter);
-  release(c->s_table); release(c->dg_hit_salt);
+  release(c->s_table); release(c->dg_hit_salt); release(c->it_state);
   release(c->hy_list); release(c->hy_lens); release(c->hy_off); release(c->hy_words);
   for (auto& e : c->dev_ev)
     if (e) (void)hipEventDestroy(e);
@@ -2797,6 +2921,11 @@ static void clear_salts(a5x_ctx* c) {
   c->s_recs.clear();
   c->s_hit_salt.clear();
   c->s_hashed = c->s_skipped = 0;
+  c->it_iters.clear();
+  c->it_tidx.clear();
+  c->it_keys.clear();
+  c->it_lines.clear();
+  c->it_by_key.clear();
 }
 
 // the built target set into the context's device buffers (a5x_set_targets, a5x_set_salted_targets)
@@ -2847,6 +2976,7 @@ int a5x_set_salted_targets(a5x_ctx* c, int algo, int order, const uint8_t* dig, 
   if (!c) return A5X_E_ARG;
   const uint32_t W = algo_size(algo);  // digest bytes
   if (!W || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
+  if (a5x_algo_pbkdf2(algo)) return fail(c, A5X_E_ARG, "digest algorithm %d is iterated (a5x_set_iterated_targets)", algo);
   if (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS)
     return fail(c, A5X_E_ARG, "salt order %d: 0 is pass.salt, 1 is salt.pass", order);
   if (algo_salted_only(algo) && order != salted_only_order(algo))
@@ -2938,14 +3068,244 @@ int a5x_set_salted_targets(a5x_ctx* c, int algo, int order, const uint8_t* dig, 
     c->t_algo = algo;
     c->n_targets = n;
   }
+  clear_salts(c);  // (an iterated set's own fields with them)
   c->salted = true;
   c->s_order = order;
   c->n_salts = S;
   c->s_bytes.swap(sb);
   c->s_off.swap(so);
   c->s_recs.swap(recs);
-  c->s_hit_salt.clear();
-  c->s_hashed = c->s_skipped = 0;
+  return A5X_OK;
+}
+
+// ---- iterated target lists (a5x_pbkdf2.h, a5x_pbkdf2.hip) ------------------------
+// a5x_set_iterated_targets; keys / lines: per target the whole key and the line of the list
+// (null: the 16 bytes, no line)
+static int set_iterated(a5x_ctx* c, int algo, const uint8_t* dig, uint64_t n, const uint8_t* salt_bytes,
+                        const uint64_t* salt_off, const uint32_t* iters, std::vector<std::vector<uint8_t>>* keys,
+                        std::vector<std::string>* lines) {
+  if (!c) return A5X_E_ARG;
+  if (!a5x_algo_pbkdf2(algo)) return fail(c, A5X_E_ARG, "digest algorithm %d is not an iterated one (72..75)", algo);
+  if (n && (!dig || !salt_off || !iters)) return fail(c, A5X_E_ARG, "null digests, salt offsets or iteration counts");
+  for (uint64_t i = 0; i < n; i++) {
+    if (salt_off[i + 1] < salt_off[i]) return fail(c, A5X_E_ARG, "salt offsets of target %llu decrease", (unsigned long long)i);
+    if (salt_off[i + 1] - salt_off[i] > A5X_SALT_MAX)
+      return fail(c, A5X_E_ARG, "salt of target %llu has %llu bytes, the limit is %u", (unsigned long long)i,
+                  (unsigned long long)(salt_off[i + 1] - salt_off[i]), A5X_SALT_MAX);
+    if (salt_off[i + 1] > salt_off[i] && !salt_bytes) return fail(c, A5X_E_ARG, "null salt bytes");
+    if (!iters[i]) return fail(c, A5X_E_ARG, "target %llu has an iteration count of 0", (unsigned long long)i);
+  }
+  if (c->n_rules)
+    return fail(c, A5X_E_UNSUPPORTED, "rules and iterated targets together are not supported: %u rules are loaded (clear them first)",
+                c->n_rules);
+  // distinct (salt, iterations) pairs, indexed by first appearance; every target's index
+  std::map<std::pair<std::string, uint32_t>, uint32_t> index;
+  std::vector<uint8_t> sb;
+  std::vector<uint64_t> so(1, 0);
+  std::vector<uint32_t> tidx(n), its;
+  for (uint64_t i = 0; i < n; i++) {
+    const size_t sl = (size_t)(salt_off[i + 1] - salt_off[i]);
+    std::string sk(sl ? (const char*)salt_bytes + salt_off[i] : "", sl);
+    auto it = index.find(std::make_pair(sk, iters[i]));
+    if (it == index.end()) {
+      it = index.emplace(std::make_pair(sk, iters[i]), (uint32_t)its.size()).first;
+      sb.insert(sb.end(), sk.begin(), sk.end());
+      so.push_back(sb.size());
+      its.push_back(iters[i]);
+    }
+    tidx[i] = it->second;
+  }
+  const uint32_t S = (uint32_t)its.size();
+  // the device table: one record per pair, sorted by salt length as the other salt tables are
+  std::vector<uint32_t> ord(S);
+  for (uint32_t i = 0; i < S; i++) ord[i] = i;
+  std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return so[x + 1] - so[x] < so[y + 1] - so[y]; });
+  std::vector<uint32_t> recs((size_t)S * A5X_PBKDF2_STRIDE, 0u);
+  for (uint32_t k = 0; k < S; k++) {
+    const uint32_t i = ord[k];
+    pbkdf2_record(algo, sb.data() + so[i], (uint32_t)(so[i + 1] - so[i]), i, its[i], &recs[(size_t)k * A5X_PBKDF2_STRIDE]);
+  }
+  if (c->device >= 0) {
+    std::vector<uint8_t> md(dig, dig + (size_t)16 * n);  // the first 16 bytes XOR the index's mask
+    for (uint64_t i = 0; i < n; i++) {
+      uint32_t m[4], d[4];
+      salt_mask(tidx[i], m);
+      memcpy(d, &md[(size_t)16 * i], 16);
+      for (int k = 0; k < 4; k++) d[k] ^= m[k];
+      memcpy(&md[(size_t)16 * i], d, 16);
+    }
+    auto upload = [&]() -> int {
+      int rc;
+      HIPCHK(c, hipSetDevice(c->device));
+      HIPCHK(c, hipStreamSynchronize(c->stream));  // (no kernel of an earlier call still reads the tables)
+      TargetSet T;
+      build_target_set(16, md.data(), n, T, dig);
+      if ((rc = upload_target_set(c, algo, n, T))) return rc;
+      if ((rc = grow(c, c->s_table, recs.size() + 1))) return rc;
+      if (S) HIPCHK(c, hipMemcpy(c->s_table.p, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
+      return A5X_OK;
+    };
+    const int rc = upload();
+    if (rc) {
+      c->t_algo = -1;
+      clear_salts(c);
+      return rc;
+    }
+  } else {
+    c->t_algo = algo;
+    c->n_targets = n;
+  }
+  clear_salts(c);
+  c->salted = true;
+  c->s_order = A5X_SALT_ORDER_PASS_SALT;
+  c->n_salts = S;
+  c->s_bytes.swap(sb);
+  c->s_off.swap(so);
+  c->s_recs.swap(recs);
+  c->it_iters.swap(its);
+  c->it_keys.resize(n);
+  for (uint64_t i = 0; i < n; i++) {
+    if (keys) c->it_keys[i].swap((*keys)[i]);
+    else c->it_keys[i].assign(dig + 16 * i, dig + 16 * i + 16);
+    std::array<uint8_t, 16> k16;
+    memcpy(k16.data(), dig + 16 * i, 16);
+    c->it_by_key[std::make_pair(tidx[i], k16)].push_back(i);
+  }
+  if (lines) c->it_lines.swap(*lines);
+  c->it_tidx.swap(tidx);
+  return A5X_OK;
+}
+
+int a5x_set_iterated_targets(a5x_ctx* c, int algo, const uint8_t* dig, uint64_t n, const uint8_t* salt_bytes,
+                             const uint64_t* salt_off, const uint32_t* iters) {
+  return set_iterated(c, algo, dig, n, salt_bytes, salt_off, iters, nullptr, nullptr);
+}
+
+static const char* pbkdf2_name(int algo) {
+  return algo == A5X_ALGO_PBKDF2_HMAC_MD5 ? "md5" : algo == A5X_ALGO_PBKDF2_HMAC_SHA1 ? "sha1"
+       : algo == A5X_ALGO_PBKDF2_HMAC_SHA256 ? "sha256" : "sha512";
+}
+// standard base64 with padding; false: not such a text
+static bool b64_decode(const uint8_t* p, size_t n, std::vector<uint8_t>& out) {
+  out.clear();
+  if (n % 4) return false;
+  auto val = [](uint8_t ch) -> int {
+    return ch >= 'A' && ch <= 'Z' ? ch - 'A' : ch >= 'a' && ch <= 'z' ? ch - 'a' + 26 : ch >= '0' && ch <= '9' ? ch - '0' + 52
+         : ch == '+' ? 62 : ch == '/' ? 63 : -1;
+  };
+  for (size_t i = 0; i < n; i += 4) {
+    int v[4], pad = 0;
+    for (int k = 0; k < 4; k++) {
+      if (p[i + k] == '=') {
+        if (i + 4 != n || k < 2) return false;
+        v[k] = 0;
+        pad++;
+      } else {
+        if (pad) return false;  // a character behind padding
+        if ((v[k] = val(p[i + k])) < 0) return false;
+      }
+    }
+    const uint32_t w = (uint32_t)v[0] << 18 | (uint32_t)v[1] << 12 | (uint32_t)v[2] << 6 | (uint32_t)v[3];
+    if ((pad == 1 && (w & 0xffu)) || (pad == 2 && (w & 0xffffu))) return false;  // (bits that decode to nothing)
+    out.push_back((uint8_t)(w >> 16));
+    if (pad < 2) out.push_back((uint8_t)(w >> 8));
+    if (pad < 1) out.push_back((uint8_t)w);
+  }
+  return true;
+}
+static std::string b64_encode(const uint8_t* p, size_t n) {
+  static const char* T = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+  std::string o;
+  for (size_t i = 0; i < n; i += 3) {
+    const uint32_t w = (uint32_t)p[i] << 16 | (i + 1 < n ? (uint32_t)p[i + 1] << 8 : 0u) | (i + 2 < n ? p[i + 2] : 0u);
+    o += T[w >> 18];
+    o += T[(w >> 12) & 63];
+    o += i + 1 < n ? T[(w >> 6) & 63] : '=';
+    o += i + 2 < n ? T[w & 63] : '=';
+  }
+  return o;
+}
+
+int a5x_load_pbkdf2_hashes(a5x_ctx* c, int algo, const uint8_t* text, size_t len, uint64_t* n_targets, uint64_t* n_salts,
+                           uint64_t* n_skipped) {
+  if (!c || (len && !text)) return A5X_E_ARG;
+  if (!a5x_algo_pbkdf2(algo)) return fail(c, A5X_E_ARG, "digest algorithm %d is not an iterated one (72..75)", algo);
+  const std::string name = pbkdf2_name(algo);
+  std::vector<uint8_t> dig, sb, salt, key;
+  std::vector<uint64_t> so(1, 0);
+  std::vector<uint32_t> its;
+  std::vector<std::vector<uint8_t>> keys;
+  std::vector<std::string> lines;
+  uint64_t bad = 0;
+  for (size_t p = 0; p < len;) {
+    size_t e = p;
+    while (e < len && text[e] != '\n') e++;
+    size_t n = e - p;
+    const uint8_t* l = text + p;
+    p = e + 1;
+    if (n && l[n - 1] == '\r') n--;
+    if (!n) continue;  // (an empty line is no target and no error)
+    // name : iterations : base64(salt) : base64(dk) -- base64 has no ':', so exactly three of them
+    size_t f[5] = {0, 0, 0, 0, n + 1};
+    int nf = 1;
+    for (size_t k = 0; k < n; k++)
+      if (l[k] == ':') {
+        if (nf < 4) f[nf] = k + 1;
+        nf++;
+      }
+    bool ok = nf == 4 && std::string((const char*)l, f[1] - 1) == name;
+    uint64_t it = 0;
+    if (ok) {
+      ok = f[2] - 1 > f[1] && f[2] - 1 - f[1] <= 10;
+      for (size_t k = f[1]; ok && k < f[2] - 1; k++) {
+        if (l[k] < '0' || l[k] > '9') ok = false;
+        else it = it * 10 + (l[k] - '0');
+      }
+      if (it == 0 || it > 0xffffffffull) ok = false;
+    }
+    ok = ok && b64_decode(l + f[2], f[3] - 1 - f[2], salt) && salt.size() <= A5X_SALT_MAX;
+    ok = ok && b64_decode(l + f[3], n - f[3], key) && key.size() >= A5X_PBKDF2_KEEP_BYTES;
+    if (!ok) { bad++; continue; }
+    dig.insert(dig.end(), key.begin(), key.begin() + 16);
+    sb.insert(sb.end(), salt.begin(), salt.end());
+    so.push_back(sb.size());
+    its.push_back((uint32_t)it);
+    keys.push_back(key);
+    lines.emplace_back((const char*)l, n);
+  }
+  const uint64_t n = its.size();
+  if (n_skipped) *n_skipped = bad;
+  const int rc = set_iterated(c, algo, dig.data(), n, sb.data(), so.data(), its.data(), &keys, &lines);
+  if (rc) return rc;
+  if (n_targets) *n_targets = n;
+  if (n_salts) *n_salts = c->n_salts;
+  return A5X_OK;
+}
+
+int a5x_salt_iterations(a5x_ctx* c, uint32_t index, uint32_t* iters) {
+  if (!c || !iters) return A5X_E_ARG;
+  if (!c->salted || index >= c->it_iters.size())
+    return fail(c, A5X_E_ARG, "index %u of %zu of an iterated set", index, c->it_iters.size());
+  *iters = c->it_iters[index];
+  return A5X_OK;
+}
+
+int a5x_debug_pbkdf2(int algo, const uint8_t* pass, size_t len, const uint8_t* salt, size_t slen, uint32_t iters,
+                     uint8_t* out, size_t dklen) {
+  if (!a5x_algo_pbkdf2(algo) || (!pass && len) || (!salt && slen) || slen > A5X_SALT_MAX || !iters || (!out && dklen))
+    return A5X_E_ARG;
+  if (len > A5X_RULE_LMAX) return A5X_E_UNSUPPORTED;
+  ShaBytes src;
+  src.p = pass;
+  src.n = (uint32_t)len;
+  return pbkdf2_host_any(algo, src, (uint32_t)len, salt, (uint32_t)slen, iters, out, dklen) ? A5X_OK : A5X_E_ARG;
+}
+
+int a5x_debug_iter_budget(a5x_ctx* c, uint64_t pair_slots, uint64_t pair_iterations, uint64_t* loop_launches) {
+  if (!c) return A5X_E_ARG;
+  c->it_slots = pair_slots;
+  c->it_pair_iters = pair_iterations;
+  if (loop_launches) *loop_launches = c->it_launches;
   return A5X_OK;
 }
 
@@ -2954,6 +3314,7 @@ int a5x_load_salted_hashes(a5x_ctx* c, int algo, int order, const uint8_t* text,
   if (!c || (len && !text)) return A5X_E_ARG;
   const uint32_t W = algo_size(algo);
   if (!W || algo_unsalted(algo)) return fail(c, A5X_E_ARG, "no salted mode for digest algorithm %d", algo);
+  if (a5x_algo_pbkdf2(algo)) return fail(c, A5X_E_ARG, "digest algorithm %d is iterated (a5x_load_pbkdf2_hashes)", algo);
   auto hexv = [](uint8_t ch) -> int {
     return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1;
   };
@@ -3056,6 +3417,51 @@ int a5x_digest_lines_salted_device(a5x_ctx* c, int algo, int order, const uint8_
   if (!nbytes) return A5X_OK;
   int rc;
   if ((rc = grow(c, c->r_counter, 2))) return rc;
+  if (a5x_algo_pbkdf2(algo)) {
+    // an iterated set: the passes of iter_stream, each ended by the compare step's op 2 twin
+    const uint32_t S = c->n_salts;
+    const uint64_t nblk = a5x_stream_blocks(nbytes);
+    uint64_t lines = 0;
+    unsigned long long skp = 0;
+    c->it_launches = 0;
+    HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, S_GUARD * sizeof(uint32_t), st));
+    HIPCHK(c, hipMemsetAsync(c->r_counter.p, 0, 8, st));
+    A5xPbkdf2Launch L;
+    memset(&L, 0, sizeof L);
+    L.s.d = dig_launch(c);
+    L.s.d.algo = algo;
+    L.s.d.out = d_lines;
+    L.s.d.nbytes = nbytes;
+    L.s.salts = c->s_table.p;
+    L.s.nsalts = S;
+    L.s.order = order;
+    L.s.skipped = c->r_counter.p;
+    auto op1 = [&] {
+      L.s.d.blk_cnt = c->dg_blk_cnt.p;
+      L.b0 = 0; L.b1 = nblk;
+      return a5x_launch_pbkdf2_init(L, 1, (uint32_t)std::max(1, c->cus), st);
+    };
+    if ((rc = stream_count_lines(c, op1, nblk, st, &lines))) return rc;
+    if (n_lines) *n_lines = lines;
+    if (lines > cap / S || !d_dig)
+      return fail(c, A5X_E_CAPACITY, "%llu lines x %u salts, digest buffer has room for %llu", (unsigned long long)lines, S,
+                  (unsigned long long)cap);
+    L.s.d.blk_pre = c->dg_blk_pre.p;
+    L.s.d.dig_out = d_dig;
+    HIPCHK(c, hipMemsetAsync(d_dig, 0, lines * S * 16, st));  // a skipped pair's bytes
+    if ((rc = iter_stream(c, L, nblk, st, [&](A5xPbkdf2Launch& Lp) -> int {
+           HIPCHK(c, a5x_launch_pbkdf2_compare(Lp, 2, st));
+           return A5X_OK;
+         })))
+      return rc;
+    HIPCHK(c, read_scalars(c, st, S_ERR));
+    HIPCHK(c, hipMemcpyAsync(&skp, c->r_counter.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (skp > lines * S) return fail(c, A5X_E_HIP, "more skipped pairs than pairs");
+    c->s_skipped = skp;
+    c->s_hashed = lines * S - skp;
+    return decode_dev_err(c, c->h_scalars[S_ERR]);
+  }
   A5xSaltLaunch SL;
   SL.salts = c->s_table.p;
   SL.nsalts = c->n_salts;
@@ -3081,7 +3487,7 @@ int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t sle
                             uint8_t* out, size_t cap) {
   const uint32_t W = algo_size(algo);
   if (!W || algo_unsalted(algo) || (order != A5X_SALT_ORDER_PASS_SALT && order != A5X_SALT_ORDER_SALT_PASS) ||
-      (!salt && slen) || (!msg && len) || !out || slen > A5X_SALT_MAX)
+      (!salt && slen) || (!msg && len) || !out || slen > A5X_SALT_MAX || a5x_algo_pbkdf2(algo))
     return A5X_E_ARG;
   if (algo_salted_only(algo) && order != salted_only_order(algo)) return A5X_E_ARG;
   if (cap < W) return A5X_E_CAPACITY;
@@ -3346,7 +3752,8 @@ int a5x_format_plain(const uint8_t* plain, size_t len, uint8_t* out, size_t cap,
 // a5x_format_hits_salted: "hexdigest:salt:plain", the salt raw or (hex_salt) in hex
 static int format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw, int mode, int mn, int mx,
                        const a5x_hit* hits, uint64_t n_hits, const uint32_t* hit_rule, a5x_sink_fn sink, void* user,
-                       const uint32_t* hit_salt = nullptr, int hex_salt = 0) {
+                       const uint32_t* hit_salt = nullptr, int hex_salt = 0, uint64_t* it_dropped = nullptr,
+                       bool iterated = false) {
   if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
   if (!c || !sink || (n_hits && (!hits || !words || !woff))) return A5X_E_ARG;
   if (!n_hits) return A5X_OK;
@@ -3461,7 +3868,48 @@ static int format_hits(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, u
   }
   static const char* hx = "0123456789abcdef";
   std::string o;
-  for (uint64_t h = 0; h < n_hits; h++) {
+  for (uint64_t h = 0; iterated && h < n_hits; h++) {
+    // An iterated set: the targets registered with the hit's index and 16 bytes; for each the
+    // whole key derived again by the host path and compared with every byte the list gave.
+    const size_t k = (size_t)(std::lower_bound(ug.begin(), ug.end(), g[h]) - ug.begin());
+    if (!c->salted || !a5x_algo_pbkdf2(c->t_algo) || hit_salt[h] >= c->n_salts)
+      return fail(c, A5X_E_ARG, "hit index %u of %u in an iterated set", hit_salt[h], c->salted ? c->n_salts : 0u);
+    if (plain[k].size() > A5X_RULE_LMAX) return fail(c, A5X_E_ARG, "hit candidate longer than 128 bytes");
+    std::array<uint8_t, 16> k16;
+    memcpy(k16.data(), hits[h].digest, 16);
+    auto it = c->it_by_key.find(std::make_pair(hit_salt[h], k16));
+    bool any = false;
+    if (it != c->it_by_key.end()) {
+      const uint32_t si = hit_salt[h];
+      const uint8_t* salt = c->s_bytes.data() + c->s_off[si];
+      const uint32_t slen = (uint32_t)(c->s_off[si + 1] - c->s_off[si]);
+      ShaBytes src;
+      src.p = (const uint8_t*)plain[k].data();
+      src.n = (uint32_t)plain[k].size();
+      size_t longest = 0;
+      for (uint64_t t : it->second) longest = std::max(longest, c->it_keys[t].size());
+      std::vector<uint8_t> dk(longest);
+      pbkdf2_host_any(c->t_algo, src, src.n, salt, slen, c->it_iters[si], dk.data(), longest);
+      for (uint64_t t : it->second) {
+        const std::vector<uint8_t>& key = c->it_keys[t];
+        if (memcmp(dk.data(), key.data(), key.size()) != 0) continue;
+        any = true;
+        if (!c->it_lines.empty()) o += c->it_lines[t];
+        else
+          o += std::string(pbkdf2_name(c->t_algo)) + ":" + std::to_string(c->it_iters[si]) + ":" + b64_encode(salt, slen) +
+               ":" + b64_encode(key.data(), key.size());
+        o += ':';
+        append_plain(o, (const uint8_t*)plain[k].data(), plain[k].size());
+        o += '\n';
+      }
+    }
+    if (!any && it_dropped) ++*it_dropped;
+    if (o.size() >= (1u << 20) || (h + 1 == n_hits && !o.empty())) {
+      if (sink(user, (const uint8_t*)o.data(), o.size())) return fail(c, A5X_E_SINK, "sink returned non-zero");
+      o.clear();
+    }
+  }
+  for (uint64_t h = 0; !iterated && h < n_hits; h++) {
     const size_t k = (size_t)(std::lower_bound(ug.begin(), ug.end(), g[h]) - ug.begin());
     for (uint32_t i = 0; i < dsz; i++) {
       o += hx[full[(size_t)dsz * h + i] >> 4];
@@ -3515,6 +3963,15 @@ int a5x_format_hits_salted(a5x_ctx* c, const uint8_t* words, const uint64_t* wof
                            a5x_sink_fn sink, void* user) {
   if (c && n_hits && !hit_salt) return fail(c, A5X_E_ARG, "no salt indices");
   return format_hits(c, words, woff, nw, mode, mn, mx, hits, n_hits, nullptr, sink, user, hit_salt, hex_salt);
+}
+
+int a5x_format_hits_iterated(a5x_ctx* c, const uint8_t* words, const uint64_t* woff, uint64_t nw, int mode, int mn,
+                             int mx, const a5x_hit* hits, uint64_t n_hits, const uint32_t* hit_salt, uint64_t* n_dropped,
+                             a5x_sink_fn sink, void* user) {
+  if (n_dropped) *n_dropped = 0;
+  if (c && n_hits && !hit_salt) return fail(c, A5X_E_ARG, "no salt indices");
+  if (c && !(c->salted && a5x_algo_pbkdf2(c->t_algo))) return fail(c, A5X_E_ARG, "the target set is not an iterated one");
+  return format_hits(c, words, woff, nw, mode, mn, mx, hits, n_hits, nullptr, sink, user, hit_salt, 0, n_dropped, true);
 }
 
 // ---- rules (a5x_rules.h, a5x_rules.hip) -----------------------------------------

@@ -294,7 +294,8 @@ constexpr uint32_t a5x_algo_words(int algo) {
        : algo == A5X_ALGO_HMAC_MD5_KEY_PASS || algo == A5X_ALGO_HMAC_MD5_KEY_SALT ? 4u  // HMAC: the hash's width
        : algo == A5X_ALGO_HMAC_SHA1_KEY_PASS || algo == A5X_ALGO_HMAC_SHA1_KEY_SALT ? 5u
        : algo == A5X_ALGO_HMAC_SHA256_KEY_PASS || algo == A5X_ALGO_HMAC_SHA256_KEY_SALT ? 8u
-       : algo == A5X_ALGO_HMAC_SHA512_KEY_PASS || algo == A5X_ALGO_HMAC_SHA512_KEY_SALT ? 16u : 0u;
+       : algo == A5X_ALGO_HMAC_SHA512_KEY_PASS || algo == A5X_ALGO_HMAC_SHA512_KEY_SALT ? 16u
+       : algo >= A5X_ALGO_PBKDF2_HMAC_MD5 && algo <= A5X_ALGO_PBKDF2_HMAC_SHA512 ? 4u : 0u;  // PBKDF2: the compared 16 bytes
 }
 // wider than the 16 bytes a table slot and a hit hold: tails compared and recorded
 constexpr bool a5x_algo_wide(int algo) { return a5x_algo_words(algo) > 4u; }
@@ -358,3 +359,28 @@ hipError_t a5x_launch_salt_nest_stream(const A5xSaltLaunch& L, int op, uint32_t 
 // = salt.  The ops are a5x_launch_salt_stream's; a pair is skipped only for a line over
 // A5X_RULE_LMAX.
 hipError_t a5x_launch_hmac_stream(const A5xSaltLaunch& L, int op, uint32_t cus, hipStream_t st);
+
+// ---- iterated target lists: PBKDF2 (a5x_pbkdf2.hip) -----------------------------
+// One pass of an iterated set (s.d.algo 72..75): the candidates of the stream blocks [b0, b1) under
+// the salt records [s0, s1) of s.salts (A5X_PBKDF2_STRIDE u32 each, a5x_pbkdf2.h).  The pair of the
+// pass's line `ord` (counted from block b0: s.d.blk_pre) and record s0 + r has slot r * np + ord of
+// the pass's `pairs` = (s1 - s0) * np slots (np: a multiple of 64 that holds the pass's lines, so a
+// wave of the flat kernels has one record); word k of slot p is state[k * pairs + p], the words
+// as Pbkdf2Cfg::STATE_WORDS lists them.  Word 1 (the ordinal in the block) is ~0 for a slot with
+// no pair: the caller sets all of them so before init.
+struct A5xPbkdf2Launch {
+  A5xSaltLaunch s;   // the stream, the target set, the hit buffer, the records, hit_salt, skipped
+  uint32_t* state;
+  uint64_t pairs;
+  uint32_t np;
+  uint64_t b0, b1;
+  uint32_t s0, s1;
+  uint32_t k0, k1;   // loop: iterations [k0, k1) (iteration j makes U_{j+1}; 1 <= k0), clipped to the pair's own count
+};
+// op 0: key states and U1 of every pair of the pass into state, += skipped pairs; op 1: line
+// starts per block (s.d.blk_cnt, all blocks of the stream)
+hipError_t a5x_launch_pbkdf2_init(const A5xPbkdf2Launch& L, int op, uint32_t cus, hipStream_t st);
+hipError_t a5x_launch_pbkdf2_loop(const A5xPbkdf2Launch& L, hipStream_t st);
+// op 0: t under the salt's mask probed, hits recorded with their index; op 2: the 16 bytes of
+// every pair to s.d.dig_out at index line * s.nsalts + public index
+hipError_t a5x_launch_pbkdf2_compare(const A5xPbkdf2Launch& L, int op, hipStream_t st);

@@ -67,6 +67,12 @@ ALGO_HMAC_SHA256_KEY_PASS = 52  # HMAC-SHA256(key = candidate, salt) (hashcat -m
 ALGO_HMAC_SHA256_KEY_SALT = 53  # HMAC-SHA256(key = salt, candidate) (hashcat -m 1460)
 ALGO_HMAC_SHA512_KEY_PASS = 54  # HMAC-SHA512(key = candidate, salt) (hashcat -m 1750)
 ALGO_HMAC_SHA512_KEY_SALT = 55  # HMAC-SHA512(key = salt, candidate) (hashcat -m 1760)
+# (56..71 are unassigned) PBKDF2 (RFC 8018) over HMAC, password = candidate: iterated sets only
+# (``Context.set_iterated_targets``), matched on the first 16 bytes of the derived key
+ALGO_PBKDF2_HMAC_MD5 = 72     # hashcat -m 11900
+ALGO_PBKDF2_HMAC_SHA1 = 73    # hashcat -m 12000
+ALGO_PBKDF2_HMAC_SHA256 = 74  # hashcat -m 10900
+ALGO_PBKDF2_HMAC_SHA512 = 75  # hashcat -m 12100
 ORDER_PASS_SALT = 0  # salted sets: hash(candidate + salt), hashcat -m 10 / 110 / 1310 / 1410 / 10810 / 1710
 ORDER_SALT_PASS = 1  # hash(salt + candidate), hashcat -m 20 / 120 / 1320 / 1420 / 10820 / 1720
 
@@ -413,6 +419,74 @@ class Context:
         self._algo_size = max(16, self._L.a5x_digest_size(algo))
         return nt.value, ns.value, sk.value
 
+    # ---- iterated target lists (a5x_pbkdf2.hip) ------------------------------------
+    def set_iterated_targets(self, algo: int, digests16, salts: Sequence[bytes], iters: Sequence[int]) -> None:
+        """Iterated target set (``ALGO_PBKDF2_HMAC_*``): target i is the first 16 bytes of the PBKDF2 key
+        under ``salts[i]`` (at most 64 bytes) and ``iters[i]`` >= 1 iterations.  Distinct (salt, iterations)
+        pairs are indexed by first appearance: ``salt_count()``, ``salt()``, ``salt_iterations()`` and
+        ``last_hit_salts()`` speak of that index."""
+        buf = np.ascontiguousarray(np.frombuffer(bytes(digests16), dtype=np.uint8) if isinstance(digests16, (bytes, bytearray))
+                                   else np.asarray(digests16, dtype=np.uint8)).reshape(-1)
+        salts = [bytes(s) for s in salts]
+        if buf.size % 16 or buf.size // 16 != len(salts) or len(iters) != len(salts):
+            raise ValueError("digests must be 16 bytes each, one salt and one iteration count per digest")
+        sb = np.frombuffer(b"".join(salts) + b"\0", dtype=np.uint8)
+        so = np.zeros(len(salts) + 1, dtype=np.uint64)
+        if salts:
+            so[1:] = np.cumsum([len(s) for s in salts])
+        it = np.ascontiguousarray(list(iters) + [0], dtype=np.uint32)
+        self._chk(self._L.a5x_set_iterated_targets(self.h, algo, buf.ctypes.data if buf.size else None, len(salts),
+                                                   sb.ctypes.data, so.ctypes.data, it.ctypes.data))
+        self._algo_size = 16
+
+    def load_pbkdf2_hashes(self, algo: int, text: bytes) -> Tuple[int, int, int]:
+        """Iterated target set from hashcat's ``name:iterations:base64(salt):base64(dk)`` lines; returns
+        (targets, distinct (salt, iterations) pairs, lines skipped)."""
+        text = text.encode() if isinstance(text, str) else bytes(text)
+        nt, ns, sk = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._L.a5x_load_pbkdf2_hashes(self.h, algo, text, len(text), ctypes.byref(nt), ctypes.byref(ns),
+                                                 ctypes.byref(sk)))
+        self._algo_size = 16
+        return nt.value, ns.value, sk.value
+
+    def salt_iterations(self, index: int) -> int:
+        """Iteration count of index ``index`` of an iterated set (beside ``salt()``)."""
+        n = ctypes.c_uint32()
+        self._chk(self._L.a5x_salt_iterations(self.h, index, ctypes.byref(n)))
+        return n.value
+
+    def iter_budget(self, pair_slots: int = 0, pair_iterations: int = 0) -> int:
+        """Test hook (``a5x_debug_iter_budget``): pair slots per pass and pair-iterations per loop launch of
+        the iterated route from now on (0: the default); returns the loop launches of the latest call."""
+        n = ctypes.c_uint64()
+        self._chk(self._L.a5x_debug_iter_budget(self.h, pair_slots, pair_iterations, ctypes.byref(n)))
+        return n.value
+
+    def format_hits_iterated(self, words: np.ndarray, offs: np.ndarray, hits, salts, mode: int = MODE_DEFAULT,
+                             mn: int = 0, mx: int = 15) -> Tuple[bytes, int]:
+        """``original-line:plain\\n`` for hits against an iterated set (a5x_format_hits_iterated): every hit's
+        whole key is derived again on the host and compared with all the list gave; returns (text, hits
+        dropped because only their first 16 bytes matched)."""
+        arr = (_lib.Hit * max(1, len(hits)))()
+        for k, (w, c, d) in enumerate(hits):
+            arr[k].word, arr[k].cand = int(w), int(c)
+            ctypes.memmove(arr[k].digest, bytes(d)[:16], 16)
+        sa = np.ascontiguousarray(salts, dtype=np.uint32)
+        if sa.size != len(hits):
+            raise ValueError("one salt index per hit")
+        chunks: List[bytes] = []
+
+        def _cb(_u, p, n):
+            chunks.append(ctypes.string_at(p, n))
+            return 0
+
+        cb = _lib.SINK(_cb)
+        dropped = ctypes.c_uint64()
+        self._chk(self._L.a5x_format_hits_iterated(self.h, words.ctypes.data, offs.ctypes.data, len(offs) - 1, mode, mn,
+                                                   mx, arr, len(hits), sa.ctypes.data if sa.size else None,
+                                                   ctypes.byref(dropped), cb, None))
+        return b"".join(chunks), dropped.value
+
     def salt_count(self) -> int:
         """Distinct salts of the current target set (0: not salted)."""
         return self._L.a5x_salt_count(self.h)
@@ -620,6 +694,15 @@ def debug_digest_salted(algo: int, order: int, salt: bytes, msg: bytes) -> bytes
     out = (ctypes.c_uint8 * 64)()
     check(_lib.load().a5x_debug_digest_salted(algo, order, salt, len(salt), msg, len(msg), out, 64))
     return bytes(out[: digest_size(algo)])
+
+
+def debug_pbkdf2(algo: int, password: bytes, salt: bytes, iters: int, dklen: int) -> bytes:
+    """``dklen`` bytes of the PBKDF2 key of an ``ALGO_PBKDF2_HMAC_*`` on the host, by the code the iterated
+    kernels run (``a5x_debug_pbkdf2``); A5xError (A5X_E_UNSUPPORTED) for a password over 128 bytes."""
+    password, salt = bytes(password), bytes(salt)
+    out = (ctypes.c_uint8 * max(1, dklen))()
+    check(_lib.load().a5x_debug_pbkdf2(algo, password, len(password), salt, len(salt), iters, out, dklen))
+    return bytes(out[:dklen])
 
 
 def partition(prefix: np.ndarray, parts: int) -> np.ndarray:

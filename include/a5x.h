@@ -69,7 +69,9 @@ enum {
  * only as salted sets (a5x_set_salted_targets), each with its own placement of the salt
  * (a5x_algo_salt_order).  39..47 are unassigned and invalid.  48..55 are HMAC (RFC 2104) with the
  * candidate as the key and the salt as the message (key = pass) or the reverse (key = salt); they
- * too exist only as salted sets, with order 0 for key = pass and 1 for key = salt. */
+ * too exist only as salted sets, with order 0 for key = pass and 1 for key = salt.  56..71 are
+ * unassigned and invalid.  72..75 are PBKDF2 (RFC 8018) over HMAC with the candidate as the
+ * password: iterated sets (a5x_set_iterated_targets), matched on the first 16 bytes of T1. */
 enum {
   A5X_ALGO_MD5 = 0,   /* RFC 1321 over the candidate bytes (== Go crypto/md5); hashcat -m 0 */
   A5X_ALGO_NTLM = 1,  /* MD4 (RFC 1320) over UTF-16LE of the candidate ([]rune + utf16.Encode); -m 1000 */
@@ -99,18 +101,22 @@ enum {
   A5X_ALGO_HMAC_SHA256_KEY_PASS = 52, /* HMAC-SHA256(K = pass, salt); -m 1450 */
   A5X_ALGO_HMAC_SHA256_KEY_SALT = 53, /* HMAC-SHA256(K = salt, pass); -m 1460 */
   A5X_ALGO_HMAC_SHA512_KEY_PASS = 54, /* HMAC-SHA512(K = pass, salt); -m 1750 */
-  A5X_ALGO_HMAC_SHA512_KEY_SALT = 55  /* HMAC-SHA512(K = salt, pass); -m 1760 */
+  A5X_ALGO_HMAC_SHA512_KEY_SALT = 55, /* HMAC-SHA512(K = salt, pass); -m 1760 */
+  A5X_ALGO_PBKDF2_HMAC_MD5 = 72,      /* PBKDF2-HMAC-MD5(pass, salt, c); hashcat -m 11900 */
+  A5X_ALGO_PBKDF2_HMAC_SHA1 = 73,     /* PBKDF2-HMAC-SHA1; -m 12000 */
+  A5X_ALGO_PBKDF2_HMAC_SHA256 = 74,   /* PBKDF2-HMAC-SHA256; -m 10900 */
+  A5X_ALGO_PBKDF2_HMAC_SHA512 = 75    /* PBKDF2-HMAC-SHA512; -m 12100 */
 };
 /* Digest bytes of an algorithm: 16, 16, 20, 32 for 0..3, 28, 48, 64 for 5..7, 16, 16, 16,
  * 16, 20, 20, 32 for 16..22, 16, 16, 16, 16, 20, 20, 20 for 32..38 (the outer digest) and 16,
- * 16, 20, 20, 32, 32, 64, 64 for 48..55; A5X_E_ARG for anything else (4, 8, 9..15, 23..31, 39..47
- * and 56 on included).  Pure host function (no HIP
- * call). */
+ * 16, 20, 20, 32, 32, 64, 64 for 48..55; 16 for 72..75 (the compared bytes of the derived key);
+ * A5X_E_ARG for anything else (4, 8, 9..15, 23..31, 39..47, 56..71 and 76 on included).  Pure
+ * host function (no HIP call). */
 A5X_API int a5x_digest_size(int algo);
 /* Where a salted nested algorithm (32..38) puts its salt: 0 text . salt (32, 34, 36, 38), 1
  * salt . text (33, 35, 37); an HMAC algorithm (48..55): 0 key = pass (48, 50, 52, 54), 1 key =
- * salt (49, 51, 53, 55) -- the `order` its salted entry points must be given.  A5X_E_ARG for
- * every other value.  Pure host function. */
+ * salt (49, 51, 53, 55) -- the `order` its salted entry points must be given; 0 for the PBKDF2
+ * algorithms 72..75.  A5X_E_ARG for every other value.  Pure host function. */
 A5X_API int a5x_algo_salt_order(int algo);
 
 /* One target hit: word index in the batch, candidate index inside that word (in the
@@ -377,7 +383,8 @@ A5X_API int a5x_format_hits_salted(a5x_ctx* ctx, const uint8_t* words, const uin
  * all zero.  digests_cap counts digests (lines x S); d_digests 4-B aligned.  Verification hook.
  * The salt records of a salted nested set (32..38) and of an HMAC set (48..55) are built for
  * its algorithm: algo must be the set's, any other algo on such a set is A5X_E_ARG, and so is
- * one of these algorithms on another kind of set. */
+ * one of these algorithms on another kind of set.  The same holds for an iterated set (72..75,
+ * order 0): 16 bytes per pair, the index being the (salt, iterations) pair's. */
 A5X_API int a5x_digest_lines_salted_device(a5x_ctx* ctx, int algo, int order, const uint8_t* d_lines, uint64_t nbytes,
                                            uint8_t* d_digests, uint64_t digests_cap, uint64_t* n_lines, void* stream);
 /* Pure host: the digest of msg + salt (order 0) or salt + msg (order 1), the message placed
@@ -390,6 +397,52 @@ A5X_API int a5x_digest_lines_salted_device(a5x_ctx* ctx, int algo, int order, co
  * over 64 bytes or the wrong order. */
 A5X_API int a5x_debug_digest_salted(int algo, int order, const uint8_t* salt, size_t slen, const uint8_t* msg,
                                     size_t len, uint8_t* out, size_t cap);
+
+/* ---- iterated target lists: PBKDF2-HMAC-MD5 / -SHA1 / -SHA256 / -SHA512 (no reference
+ * counterpart: hashcat -m 11900 / 12000 / 10900 / 12100) ---------------------------------- */
+/* Replace the target set with an iterated one: algo 72..75, n targets of 16 bytes each (the
+ * first 16 bytes of the derived key's block T1 -- what hashcat compares), target i registered
+ * with the salt salt_bytes[salt_off[i] .. salt_off[i+1]) (at most 64 bytes) and iters[i] >= 1
+ * iterations.  Distinct (salt, iterations) pairs are deduplicated and indexed by first
+ * appearance; that index is what a5x_salt_count / a5x_salt_get / a5x_salt_iterations /
+ * a5x_hit_salts speak of.  The set is a salted one of order 0: every a5x_expand_digest* call
+ * derives a key per (candidate, index) pair, a candidate over 128 bytes is skipped under every
+ * index and counted (a5x_salts_last), a candidate of 65..128 bytes as the key of a 64-byte-block
+ * hash is replaced by its digest.  A5X_E_ARG: an iteration count of 0, a salt over 64 bytes, an
+ * algo other than 72..75; A5X_E_UNSUPPORTED: the context holds rules (a5x_set_rules on such a
+ * set answers the same).  A host-only context checks the arguments and keeps them.
+ * a5x_set_targets, a5x_set_salted_targets and a5x_debug_digest_salted answer A5X_E_ARG for
+ * 72..75. */
+A5X_API int a5x_set_iterated_targets(a5x_ctx* ctx, int algo, const uint8_t* digests16, uint64_t n,
+                                     const uint8_t* salt_bytes, const uint64_t* salt_off, const uint32_t* iters);
+/* The same from hashcat's lines "name:iterations:base64(salt):base64(dk)", name = md5 / sha1 /
+ * sha256 / sha512 as algo says, standard base64 with padding ('\n', one trailing '\r' dropped,
+ * empty lines ignored).  A line is skipped and counted in *n_skipped for a wrong name, bad
+ * base64, iterations 0 or not a number, a salt over 64 bytes or a key under 16 bytes.  The
+ * original line and the whole key are kept per target for a5x_format_hits_iterated. */
+A5X_API int a5x_load_pbkdf2_hashes(a5x_ctx* ctx, int algo, const uint8_t* text, size_t len, uint64_t* n_targets,
+                                   uint64_t* n_salts, uint64_t* n_skipped);
+/* The iteration count of index `index` of the context's iterated set (beside a5x_salt_get). */
+A5X_API int a5x_salt_iterations(a5x_ctx* ctx, uint32_t index, uint32_t* iters);
+/* a5x_format_hits for an iterated set, "original-line:plain\n" (a set given by
+ * a5x_set_iterated_targets has no lines: "name:iterations:base64(salt):base64(16 bytes)" is
+ * written in their place).  Before a hit is printed the whole derived key is computed again on
+ * the host, by the code the kernels run, and compared with every byte the list gave: a hit that
+ * matched 16 bytes but not the rest is dropped and counted in *n_dropped (NULL: not wanted). */
+A5X_API int a5x_format_hits_iterated(a5x_ctx* ctx, const uint8_t* words, const uint64_t* word_off, uint64_t n_words,
+                                     int mode, int min, int max, const a5x_hit* hits, uint64_t n_hits,
+                                     const uint32_t* hit_salt, uint64_t* n_dropped, a5x_sink_fn sink, void* user);
+/* Pure host: dklen bytes of the PBKDF2 key of algo 72..75, all blocks T1..Tn, by the host path
+ * of a5x_pbkdf2.h.  A5X_E_UNSUPPORTED for a candidate over 128 bytes; A5X_E_ARG for iters 0, a
+ * salt over 64 bytes or another algo. */
+A5X_API int a5x_debug_pbkdf2(int algo, const uint8_t* pass, size_t len, const uint8_t* salt, size_t slen,
+                             uint32_t iters, uint8_t* out, size_t dklen);
+/* Test hook of the iterated route's slicing: at most pair_slots pair slots per pass and
+ * pair_iterations pair-iterations per loop launch from now on (0: the default is kept or
+ * restored); *loop_launches (NULL: not wanted) = the loop launches of the context's latest
+ * a5x_expand_digest* or a5x_digest_lines_salted_device call on an iterated set. */
+A5X_API int a5x_debug_iter_budget(a5x_ctx* ctx, uint64_t pair_slots, uint64_t pair_iterations,
+                                  uint64_t* loop_launches);
 
 /* Output byte offset, in the batch's full "cand\n" stream, of each global candidate index
  * cands[i] (cands[i] = the batch's total candidates gives its total bytes; larger: clamped).
