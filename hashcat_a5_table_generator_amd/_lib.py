@@ -20,6 +20,7 @@ ERRORS = {
     -10: "A5X_E_NOTABLE", -11: "A5X_E_SINK",
 }
 E_CAPACITY = -8
+CUT_ONCE_OUT, CUT_ONCE_REC = 29, 1297  # A5X_CUT_ONCE_OUT / A5X_CUT_ONCE_REC (a5x_debug_cut_once)
 
 # the exported symbols of include/a5x.h (checked by tests/test_abi.py)
 EXPORTS = (
@@ -28,7 +29,7 @@ EXPORTS = (
     "a5x_split_words", "a5x_keyspace", "a5x_expand", "a5x_expand_range", "a5x_expand_device", "a5x_keyspace_device",
     "a5x_digest_device", "a5x_partition", "a5x_dev_alloc", "a5x_dev_free", "a5x_memcpy_h2d",
     "a5x_memcpy_d2h", "a5x_synchronize", "a5x_debug_stamps", "a5x_debug_plan_word", "a5x_debug_plan_sizes",
-    "a5x_debug_piece_build", "a5x_debug_cplx_build", "a5x_debug_keyspace_cplx_lean",
+    "a5x_debug_piece_build", "a5x_debug_cut_once", "a5x_debug_cplx_build", "a5x_debug_keyspace_cplx_lean",
     "a5x_debug_keyspace_refit", "a5x_debug_keyspace_small_stage", "a5x_debug_keyspace_stage",
     "a5x_debug_keyspace_large_stage",
     "a5x_set_targets", "a5x_expand_digest", "a5x_expand_digest_device", "a5x_expand_digest_range_device",
@@ -123,6 +124,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         L.a5x_debug_plan_sizes.argtypes = [vp, vp, sz, vp]
     if hasattr(L, "a5x_debug_piece_build"):
         L.a5x_debug_piece_build.argtypes = [vp, vp, sz, vp]
+    if hasattr(L, "a5x_debug_cut_once"):
+        L.a5x_debug_cut_once.argtypes = [vp, vp, sz, vp, vp, vp]
     if hasattr(L, "a5x_debug_cplx_build"):
         L.a5x_debug_cplx_build.argtypes = [vp, vp, sz, i, i, vp]
         L.a5x_debug_keyspace_cplx_lean.argtypes = [vp, ctypes.POINTER(u64)]

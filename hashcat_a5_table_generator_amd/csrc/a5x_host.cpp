@@ -2898,6 +2898,21 @@ int a5x_debug_piece_build(a5x_ctx* c, const uint8_t* word, size_t len, uint32_t*
   return A5X_OK;
 }
 
+int a5x_debug_cut_once(a5x_ctx* c, const uint8_t* word, size_t len, uint32_t* out, uint64_t* rec_new, uint64_t* rec_ref) {
+  static_assert(A5X_CUT_ONCE_OUT == CO_NOUT && A5X_CUT_ONCE_REC == CO_NREC, "a5x.h and a5x_plan.h");
+  if (!c || !out || (!word && len)) return A5X_E_ARG;
+  if (len > 127) return fail(c, A5X_E_ARG, "word of %zu bytes (the cut-once check takes <= 127)", len);
+  if (c->table.keys.empty()) return fail(c, A5X_E_NOTABLE, "no substitution table loaded");
+  if (c->table_dirty || c->blob.empty()) {
+    int rc = compile_table(c);
+    if (rc) return rc;
+  }
+  std::vector<uint8_t> wb(word, word + len);
+  wb.resize(len + 16, 0);
+  cut_once_compare(wb.data(), (u32)len, tab_view(c->blob.data()), out, rec_new, rec_ref);
+  return A5X_OK;
+}
+
 int a5x_debug_cplx_build(a5x_ctx* c, const uint8_t* word, size_t len, int mn, int mx, uint32_t* out) {
   if (!c || !out || (!word && len)) return A5X_E_ARG;
   if (len > 127) return fail(c, A5X_E_ARG, "word of %zu bytes (the complex-word check takes <= 127)", len);

@@ -293,9 +293,9 @@ __device__ __forceinline__ u32 wave_append(bool pred, u32* ctr) {
 
 #ifndef KS_ABL
 #define KS_ABL 0  // keyspace timing ablations (variant builds only, wrong output): 1 no build pass,
-                  // 4 no record stores, 8 the replayed words' cuts but no group entries (2, no
-                  // planner in the count pass, is gone: the build pass checks its plan against
-                  // the count pass's, so it never gave a figure)
+                  // 4 no record stores, 8 the logged words' literal pieces and header but no group
+                  // entries (2, no planner in the count pass, is gone: the build pass works
+                  // from the count pass's cuts)
 #endif
 
 #ifndef KC_ABL
@@ -637,9 +637,11 @@ __device__ __forceinline__ u32 ks_sort_tile(u32 key, u32 info, u32* sinfo, uint8
 // in word order inside the tile's record region (workgroup scan of the sizes).
 // The tile's word bytes are staged in LDS with 16-B loads.
 // Lane tid detects the lone matches of word tid (psk_detect); then the tile is sorted by
-// unit count (ks_sort_tile) and the lane works on the word it owns: the unit loops of the
-// count pass (psk_units) and of the build pass (the replay) run to the wave's largest unit
-// count, which the sort makes 3 / 4 / 6 / 10 on a dictionary instead of 9-10 in every wave.
+// unit count (ks_sort_tile) and the lane works on the word it owns: the unit loop of the
+// count pass (psk_units) runs to the wave's largest unit count, which the sort makes
+// 3 / 4 / 6 / 10 on a dictionary instead of 9-10 in every wave.  A word is cut into pieces
+// once, there: the count pass leaves a descriptor per group (CutPlanner), and the build pass
+// is one loop over the descriptors to the wave's largest group count.
 // Everything per word (counts, flags, lists, records, the vocc row) goes through the owned
 // word's index; nothing else depends on which lane did the work.
 // The word stage is a.wstage bytes: KS_WB, or the batch's small stage (a5x_keyspace_small_stage)
@@ -726,6 +728,7 @@ __device__ __forceinline__ void ks_thread_tiles(const KsArgs& a) {
     // tid owns word own (a stable counting sort, so the order is the same in every run) ----
     const u32 own = ks_sort_tile(key, info, sinfo, sperm, shist, tid, lane, wv, ks_rot);
     info = sinfo[own];
+    __syncthreads();  // the count pass leaves its group descriptors in gbuf, where sinfo lies
     const u64 w = t0 + own;
     const bool valid = (info >> 26) & 1u, longw = (info >> 27) & 1u, trivial = (info >> 28) & 1u;
     const bool psk = (info >> 29) & 1u;
@@ -735,10 +738,13 @@ __device__ __forceinline__ void ks_thread_tiles(const KsArgs& a) {
     LWord lw;
     lw.base = wb; lw.off = info & 0x3FFFu;
     const uint16_t* ulog_c = ulog + own;  // the owned word's log column
-    // ---- pass 1: units -> counts + piece plan (count mode) ----
+    // ---- pass 1: units -> counts + piece plan (count mode), the cuts kept: one descriptor
+    // per closed group in the lane's slice of gbuf (CutPlanner) ----
     CountAcc A;
     count_init(A, L);
-    CountPlanner<KS_GCAP> pl;
+    DevRecSink sk;
+    sk.g = gbuf + tid; sk.c = sk.g; sk.rec = nullptr; sk.np = 0;  // no clusters here
+    CutPlanner<DevRecSink, KS_GCAP> pl(sk);
     const bool rm = a.rmode != 0;
     bool rep = false;  // (-s / -s -r with vocc: a repeated pattern; the occurrences logged)
     const bool refit = nlog > KS_ULOG;  // the log does not hold the word
@@ -792,36 +798,29 @@ __device__ __forceinline__ void ks_thread_tiles(const KsArgs& a) {
     // ---- pass 2: the records of the FAST words (same walk, build mode) ----
     {
       u64* rec = a.rec + tile * FW_TILE_REC + ro;
-      DevRecSink sk;
-      sk.g = gbuf + tid; sk.c = sk.g; sk.rec = rec; sk.np = ff_np(f);  // no clusters here
-      // replay the logged units (no second byte walk): the cuts per unit, then every group's
+      sk.rec = rec; sk.np = ff_np(f);
+      // the words of the unit log: no unit is looked at again.  One loop over the group
+      // descriptors of the count pass: the literal pieces before a group, then the group's
       // entries once per piece (PieceBuilder); words with more units re-walk
       const bool replay = nlog <= KS_ULOG;
       const bool rebuild = build && replay && !(KS_ABL & 1);
       {
         const ULogCol lg{ulog_c};
         PieceBuilder<LWord, DevRecSink, ULogCol, KS_GCAP> pc(lw, T, sk, lg);
-        const u32 nrep = rebuild ? nlog : 0u;
-        for (u32 i = 0; i < wave_max_u32(nrep); i++) {
-          if (i < nrep) {
-            const u32 e = ulog_c[i * 256u];
-            Unit U;
-            lone_unit(T, e >> 10, e & 1023u, U);
-            u64 seen = 0;
-            if (rm) (void)mode_unit(T, U, a.rmode, seen, false);  // (qualified in the count pass)
-            pc.unit(U);
+        // (a group list of 8: np <= FW_PMAX for a FAST word)
+        const u32 ngr = rebuild ? umin32(ff_ng(f), 8u) : 0u;
+        for (u32 g = 0; g < wave_max_u32(ngr); g++) {
+          if (g < ngr) {
+            pc.place_cuts(g);
+            if (!(KS_ABL & 8)) pc.build_group(g, L);
           }
         }
-        if (rebuild) pc.finish(L);
-        const Plan& P = pc.P;
-        // (a group list of 8: np <= FW_PMAX for a FAST word, and a plan that disagrees with
-        // the count pass's is reported below whatever was built)
-        const u32 ngr = rebuild && P.ok && !(KS_ABL & 8) ? umin32(P.ng, 8u) : 0u;
-        for (u32 g = 0; g < wave_max_u32(ngr); g++)
-          if (g < ngr) pc.build_group(g, L);
         if (rebuild) {
+          pc.place_tail(L);
+          const Plan& P = pc.P;
           rec[0] = fr_hdr(P.np, P.ng, P.ne, P.maxl, P.nbig, P.bstarts, P.bRp);
-          if (!P.ok || P.ng != ff_ng(f) || P.ne != ff_ne(f) || P.np != ff_np(f)) atomicOr(a.err, A5X_DERR_STATE);
+          // what was placed against the count pass's sizes
+          if (pc.mis || P.ng != ff_ng(f) || P.ne != ff_ne(f) || P.np != ff_np(f)) atomicOr(a.err, A5X_DERR_STATE);
           a.roff[w] = (u32)(tile * FW_TILE_REC + ro);
         }
       }

@@ -584,7 +584,8 @@ struct Planner {
   }
 };
 
-// The count pass of k_keyspace_thread: Planner<false> reduced to what the class decision
+// The count pass of k_keyspace_cplx's lean path, and through CutPlanner (below, which adds the
+// group descriptors) of k_keyspace_thread: Planner<false> reduced to what the class decision
 // (classify_finish: ok, np, ne, maxl, minl, nbig, bent) and the FAST flag fields (np, ng,
 // ne) read.  No piece starts, literal bytes, big-piece starts or packed R, no balanced
 // grouping; a run of literal pieces is accounted in closed form (nothing is stored per
@@ -698,6 +699,9 @@ A5X_HD u32 fr_magic8(u32 R) {
 //   off | first unit << 7 | members << 15 | tail << 17 | first entry << 18 (10 bits) |
 //   (R - 1) of members 0..2 << 30 (3 bits each; 0 past the last member) | piece << 39
 // (the fields hold any word of <= 127 bytes with <= 8 groups, FAST or not: the host check)
+// CutPlanner, which leaves the same descriptors from the count pass, adds what place_cuts
+// needs to put the literal pieces and the header together without the units:
+//   the byte where the last member ends << 46 (7 bits) | the longest entry's bytes << 53 (3 bits)
 // build_group(g, L) then writes the group's entries and piece descriptor once, from
 // registers.  Literal pieces are written where they are cut, as Planner::literal does.
 // a5x_debug_piece_build / tests/test_plan_piece_build.py compare the records of the two.
@@ -713,11 +717,12 @@ struct PieceBuilder {
   u32 cR, cmax, prev; // cR = 0: no open group
   u32 nu;             // units taken (the log index of the next)
   u64 gd;             // the open group's descriptor
+  u32 tj, mis;        // place_cuts: the last group took the tail; groups not where their descriptors say
 
   A5X_HD PieceBuilder(const W& w, const Tab& t, S& s, const LG& lg) : wd(w), T(t), sk(s), ul(lg) {
     P.np = 0; P.ng = 0; P.ne = 0; P.lconst = 0; P.maxl = 0; P.minl = 0; P.ok = true;
     P.nbig = 0; P.bstarts = 0; P.bent = 0; P.bRp = 0;
-    bR = 1; bl = 0; bspan = 0; cR = 0; cmax = 0; prev = 0; nu = 0; gd = 0;
+    bR = 1; bl = 0; bspan = 0; cR = 0; cmax = 0; prev = 0; nu = 0; gd = 0; tj = 0; mis = 0;
   }
   // Planner::big_join (FB_RMAX) for a small piece pi that exists when c
   A5X_HD void big(u32 R, u32 maxlen, u32 pi, bool c) {
@@ -775,6 +780,41 @@ struct PieceBuilder {
     cmax += tm ? tl : 0u;
     close_group(open, tm);
     u32 off = prev, rem = tm ? 0u : tl;
+    while (rem) {
+      const u32 n = umin32(FW_PLEN, rem);
+      literal(off, n, n == rem);
+      off += n; rem -= n;
+    }
+  }
+  // The build pass from the descriptors that the count pass left (CutPlanner below: unit() /
+  // finish() above are not run, the cuts are made once).  place_cuts(g), g = 0, 1, ... in
+  // order: the literal pieces between the end of group g - 1 (the word's start) and group g's
+  // first byte -- full FW_PLEN pieces, then the rest, as the splitting loop of unit() cuts
+  // them -- and group g itself into the plan: its piece and entries are counted, its big
+  // piece joined (R the product of its members', its longest entry from the descriptor).
+  // build_group(g, L) writes the group as before.  place_tail(L) after the last group: the
+  // tail's literal pieces ('\n' last) when no group took the tail.  P then holds what
+  // unit() / finish() leave (np, ng, ne, maxl and the header's nbig, bstarts, bRp), and mis
+  // counts the groups whose descriptor names another piece or first entry than the pieces
+  // placed before it give.
+  A5X_HD void place_cuts(u32 g) {
+    const u64 d = sk.gld(0, g & 7u);
+    const u32 off = (u32)d & 127u;
+    for (u32 o = prev; o < off;) {
+      const u32 n = umin32(FW_PLEN, off - o);
+      literal(o, n, false);
+      o += n;
+    }
+    const u32 R = (((u32)(d >> 30) & 7u) + 1u) * (((u32)(d >> 33) & 7u) + 1u) * (((u32)(d >> 36) & 7u) + 1u);
+    const u32 cm = (u32)(d >> 53) & 7u;
+    mis += ((u32)(d >> 39) & 127u) != P.np || ((u32)(d >> 18) & 1023u) != P.ne ? 1u : 0u;
+    big(R, cm, P.np, true);
+    P.ne += R; P.ng++; P.np++; P.maxl += cm;
+    prev = (u32)(d >> 46) & 127u;
+    tj = (u32)(d >> 17) & 1u;
+  }
+  A5X_HD void place_tail(u32 L) {
+    u32 off = prev, rem = tj ? 0u : L - prev + 1u;
     while (rem) {
       const u32 n = umin32(FW_PLEN, rem);
       literal(off, n, n == rem);
@@ -855,6 +895,65 @@ struct PieceBuilder {
       d1 = w1 ? 0u : d1; d2 += w1 ? 1u : 0u;
     }
     sk.desc(pi, (u64)fr_magic8(cRg) | ((u64)(ebase & 255u) << 32) | ((u64)(cRg - 1u) << 40));
+  }
+};
+
+// The count pass of k_keyspace_thread that keeps its cuts: CountPlanner (the same P and
+// refused count, field by field) which also leaves the descriptor of every group it closes
+// in the sink's group buffer (gst(0, g & 7, .): PieceBuilder's descriptor with the two
+// fields place_cuts reads), so that the build pass makes no cut of its own.  Straight-line
+// as CountPlanner::unit is; nothing is stored per unit or per literal, one store per group.
+// After a refused unit, or past 8 groups, the descriptors are not meaningful (the word is
+// not FAST and nothing reads them); the stores stay in the lane's 8 slots.
+// a5x_debug_cut_once / tests/test_plan_cut_once.py compare it with CountPlanner, and the
+// record built from its descriptors with Planner<true, ., ., 8>'s.
+template <class S, u32 CAP = 8>
+struct CutPlanner : CountPlanner<CAP> {
+  static_assert(CAP <= 8, "3-bit R - 1 fields, <= 3 members");
+  typedef CountPlanner<CAP> B;
+  S& sk;
+  u64 gd;  // the open group's descriptor
+  u32 nu;  // units taken (the log index of the next)
+
+  A5X_HD explicit CutPlanner(S& s) : sk(s), gd(0), nu(0) {}
+  A5X_HD void close_cut(bool c, bool tail) {
+    if (c) sk.gst(0, this->P.ng & 7u, gd | ((u64)tail << 17) | ((u64)(this->cmax & 7u) << 53));
+    B::close_group(c);
+  }
+  A5X_HD void unit(const Unit& U) {  // CountPlanner::unit, with the descriptor
+    const u32 Ru = U.R, ml = U.ml, run = U.s - this->prev;
+    this->refused += U.ok && ml <= FW_PLEN && Ru <= CAP && Ru >= 2 ? 0u : 1u;
+    const bool open = this->cR != 0, merge = open && this->cmax + run + ml <= FW_PLEN && this->cR * Ru <= CAP;
+    close_cut(open && !merge, false);
+    const bool split = !merge && run + ml > FW_PLEN;
+    const u32 m = split ? (run - (ml ? 0u : 1u)) / FW_PLEN : 0u, rest = run - m * FW_PLEN;
+    const bool part = split && rest + ml > FW_PLEN;
+    this->lits(m, part ? rest : 0u);
+    const u32 rem = part ? 0u : rest;
+    const u32 nm = (u32)(gd >> 15) & 3u;  // members of the open group
+    const u32 r1 = (Ru - 1u) & 7u;
+    const u64 fresh = (u64)((U.s - rem) & 127u) | ((u64)(nu & 255u) << 7) | (1ull << 15) |
+                      ((u64)(this->P.ne & 1023u) << 18) | ((u64)r1 << 30) | ((u64)(this->P.np & 127u) << 39);
+    gd = (merge ? ((gd & ~(127ull << 46)) + (1ull << 15)) | ((u64)r1 << (30u + 3u * nm)) : fresh) |
+         ((u64)(U.e & 127u) << 46);
+    this->cR = merge ? this->cR * Ru : Ru;
+    this->cmax = merge ? this->cmax + run + ml : rem + ml;
+    this->cmin = merge ? this->cmin + run + U.mnl : rem + U.mnl;
+    this->P.np += merge ? 0u : 1u;
+    this->prev = U.e;
+    nu++;
+  }
+  A5X_HD void finish(u32 L) {  // tail bytes + '\n'
+    this->P.ok = this->refused == 0;
+    if (!this->P.ok) return;
+    const u32 tl = L - this->prev + 1;
+    if (this->cR && this->cmax + tl <= FW_PLEN) {
+      this->cmax += tl; this->cmin += tl;
+      close_cut(true, true);
+    } else {
+      if (this->cR) close_cut(true, false);
+      this->lits(tl / FW_PLEN, tl % FW_PLEN);
+    }
   }
 };
 
@@ -1134,6 +1233,104 @@ inline void piece_build_compare(const uint8_t* wd, u32 L, const Tab& T, uint32_t
   rb[0] = fr_hdr(pb.P.np, pb.P.ng, pb.P.ne, pb.P.maxl, pb.P.nbig, pb.P.bstarts, pb.P.bRp);
   bool eq = pa.P.bent == pb.P.bent && pa.P.np == cp.P.np && pa.P.ne == cp.P.ne && pa.P.ng == cp.P.ng;
   for (u32 i = 0; i < NREC; i++) eq = eq && ra[i] == rb[i];
+  out[0] = eq ? PB_EQUAL : PB_DIFFERENT;
+}
+
+// Host check of the cut-once path of k_keyspace_thread on one word (a5x_debug_cut_once,
+// tools/cut_once_selftest.cpp): the count pass with CutPlanner, then the record from its
+// descriptors alone (place_cuts / build_group / place_tail), against CountPlanner<8> and
+// Planner<true, ., ., 8>.  wd and the result codes as for piece_build_compare.
+//   out[0..8]    as piece_build_compare (np, ng, ne, members, tails, literals of the new
+//                path's plan; FAST by CountPlanner and classify_finish alone)
+//   out[9]       u64 of the record (1 + np + ne) when compared, else 0
+//   out[10..18]  CutPlanner:   ok np ng ne maxl minl nbig bent refused
+//   out[19..27]  CountPlanner: the same
+//   out[28]      groups of the reference planner (Planner<true, ., ., 8>)
+// rnew / rref (CO_NREC u64 each, may be null): the two records, zero past their ends.
+#define CO_NREC (1 + 128 + 128 * 8 + 128 + 16)
+#define CO_NOUT 29
+inline void cut_once_compare(const uint8_t* wd, u32 L, const Tab& T, uint32_t* out, u64* rnew, u64* rref) {
+  static_assert(CO_NREC >= 1 + 128 + 1023 + 8, "the builder's masked entry indices stay inside");
+  for (int j = 0; j < CO_NOUT; j++) out[j] = 0;
+  u64 ra[CO_NREC], rb[CO_NREC];
+  for (u32 i = 0; i < CO_NREC; i++) ra[i] = rb[i] = 0;
+  auto give = [&]() {
+    for (u32 i = 0; i < CO_NREC; i++) {
+      if (rref) rref[i] = ra[i];
+      if (rnew) rnew[i] = rb[i];
+    }
+  };
+  give();
+  GWord gw;
+  gw.p = wd;
+  u32 log[128], nu = 0, p = 0;
+  bool na = false;
+  CountAcc A;
+  count_init(A, L);
+  ArraySink sa, sb;
+  sa.rec = ra; sb.rec = rb; sa.np = sb.np = 128u;
+  for (u32 i = 0; i < FW_UMAXR; i++) sa.g[i] = sa.c[i] = sb.g[i] = sb.c[i] = 0;
+  CountPlanner<8> cp;
+  CutPlanner<ArraySink, 8> ct(sb);
+  Unit U;
+  while (next_unit(gw, L, p, T, U)) {
+    if (U.k || !U.ok || U.key >= 1024u || nu >= 128u) { na = true; break; }
+    log[nu++] = (U.s << 10) | U.key;
+    count_unit(A, U);
+    cp.unit(U);
+    ct.unit(U);
+  }
+  out[0] = PB_NA; out[1] = nu;
+  if (na) return;
+  cp.finish(L);
+  ct.finish(L);
+  const Plan* pp[2] = {&ct.P, &cp.P};
+  for (int k = 0; k < 2; k++) {
+    uint32_t* o = out + 10 + 9 * k;
+    const Plan& Q = *pp[k];
+    o[0] = Q.ok; o[1] = Q.np; o[2] = Q.ng; o[3] = Q.ne; o[4] = Q.maxl; o[5] = Q.minl; o[6] = Q.nbig; o[7] = Q.bent;
+    o[8] = k ? cp.refused : ct.refused;
+  }
+  bool same = true;  // (after a refused unit only ok and the refused count mean anything)
+  for (int j = 0; j < 9; j++) same = same && (out[10 + j] == out[19 + j] || (!cp.P.ok && j >= 1 && j <= 7));
+  sa.np = sb.np = cp.P.ok ? cp.P.np : 128u;
+  Planner<true, GWord, ArraySink, 8> pa(gw, T, sa);
+  for (u32 i = 0; i < nu; i++) {
+    lone_unit(T, log[i] >> 10, log[i] & 1023u, U);
+    pa.unit(U);
+  }
+  pa.finish(L);
+  out[28] = pa.P.ok ? pa.P.ng : 0u;
+  if (!pa.P.ok || !cp.P.ok) {
+    out[0] = !pa.P.ok && !cp.P.ok && same ? PB_NA : PB_DIFFERENT;
+    return;
+  }
+  const WordClass C = classify_finish(A, cp.P, L, 0, 1 << 30, A5X_RING_A - 16);
+  out[8] = (C.flags & A5X_WF_FAST) && !(C.flags & A5X_WF_DEFER) ? 1u : 0u;
+  out[2] = ct.P.np; out[3] = ct.P.ng; out[4] = ct.P.ne; out[7] = ct.P.np - ct.P.ng;
+  if (cp.P.ng > 8u || ct.P.ng > 8u) {
+    out[0] = out[8] || !same ? PB_DIFFERENT : PB_NOTFAST;  // (a FAST word has <= FW_PMAX pieces)
+    return;
+  }
+  ULogArr lg;
+  lg.p = log;
+  PieceBuilder<GWord, ArraySink, ULogArr, 8> pb(gw, T, sb, lg);
+  for (u32 g = 0; g < ct.P.ng; g++) {
+    const u64 d = sb.gld(0, g);
+    out[5] = umax32(out[5], (u32)(d >> 15) & 3u);
+    out[6] += (u32)(d >> 17) & 1u;
+    pb.place_cuts(g);
+    pb.build_group(g, L);
+  }
+  pb.place_tail(L);
+  ra[0] = fr_hdr(pa.P.np, pa.P.ng, pa.P.ne, pa.P.maxl, pa.P.nbig, pa.P.bstarts, pa.P.bRp);
+  rb[0] = fr_hdr(pb.P.np, pb.P.ng, pb.P.ne, pb.P.maxl, pb.P.nbig, pb.P.bstarts, pb.P.bRp);
+  out[9] = 1u + pa.P.np + pa.P.ne;
+  // what was placed against the count pass, as the kernel checks it
+  bool eq = same && pb.mis == 0 && pb.P.np == cp.P.np && pb.P.ne == cp.P.ne && pb.P.ng == cp.P.ng &&
+            pb.P.nbig == cp.P.nbig && pb.P.bent == cp.P.bent && pb.P.maxl == cp.P.maxl && pa.P.bent == cp.P.bent;
+  for (u32 i = 0; i < CO_NREC; i++) eq = eq && ra[i] == rb[i];
+  give();
   out[0] = eq ? PB_EQUAL : PB_DIFFERENT;
 }
 

@@ -598,6 +598,20 @@ class Context:
         self._chk(self._L.a5x_debug_keyspace_refit(self.h, ctypes.byref(n)))
         return n.value
 
+    def cut_once(self, word: bytes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(out, rec_new, rec_ref) of ``a5x_debug_cut_once`` for one word of <= 127 bytes, on the
+        host (``Context(-1)`` will do): the count pass of ``k_keyspace_thread`` that keeps its
+        cuts and the record built from them, against the planners it replaces (a test hook;
+        the fields of ``out`` are listed in ``include/a5x.h``)."""
+        word = bytes(word)
+        wb = np.frombuffer(word + b"\0", dtype=np.uint8)
+        out = np.zeros(_lib.CUT_ONCE_OUT, dtype=np.uint32)
+        rn = np.zeros(_lib.CUT_ONCE_REC, dtype=np.uint64)
+        rr = np.zeros(_lib.CUT_ONCE_REC, dtype=np.uint64)
+        self._chk(self._L.a5x_debug_cut_once(self.h, wb.ctypes.data, len(word), out.ctypes.data, rn.ctypes.data,
+                                             rr.ctypes.data))
+        return out, rn, rr
+
     def keyspace_cplx_lean(self) -> Tuple[int, int]:
         """(lean, generic): the words of the last keyspace pass that ``k_keyspace_cplx`` took by
         its lean path and by its generic unit walk (``a5x_debug_keyspace_cplx_lean``; a test hook)."""

@@ -501,6 +501,22 @@ A5X_API int a5x_debug_plan_sizes(a5x_ctx* ctx, const uint8_t* word, size_t len, 
  * when the word is FAST. */
 A5X_API int a5x_debug_piece_build(a5x_ctx* ctx, const uint8_t* word, size_t len, uint32_t* out);
 
+/* Test hook (CPU test suite): ONE word (<= 127 bytes) of lone matches by the cut-once path
+ * of k_keyspace_thread -- the count pass that keeps one descriptor per group, then the record
+ * built from those descriptors alone, no unit looked at again -- against the count-pass
+ * planner it replaces and the build-mode planner with groups of <= 8 entries.
+ * out[A5X_CUT_ONCE_OUT]: out[0..8] as a5x_debug_piece_build (0 = records and count-pass fields
+ * equal, 1 different, 2 not applicable, 3 not FAST and more than 8 group pieces; "FAST" by the
+ * reference planners alone); out[9] = u64 of the record, 0 when none was compared;
+ * out[10..18] = ok, np, ng, ne, maxl, minl, nbig, big entries, refused units of the new count
+ * pass; out[19..27] = the same of the planner it replaces; out[28] = group pieces of the
+ * build-mode planner.  rec_new / rec_ref (A5X_CUT_ONCE_REC u64 each, or null): the record of
+ * the new path and of the build-mode planner, zero past their ends. */
+#define A5X_CUT_ONCE_OUT 29
+#define A5X_CUT_ONCE_REC 1297
+A5X_API int a5x_debug_cut_once(a5x_ctx* ctx, const uint8_t* word, size_t len, uint32_t* out, uint64_t* rec_new,
+                               uint64_t* rec_ref);
+
 /* Test hook (GPU test suite): how many words of the context's last keyspace pass (any
  * a5x_keyspace* / a5x_expand* call, every mode) k_keyspace_thread could not hold in its
  * per-word unit log (more than 16 lone matches, a match at byte >= 64, a key index
