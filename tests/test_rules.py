@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 
 import rule_oracle as ro
+# the grammar of the random rules and words, shared with the rule corpus
+from rule_fuzz import random_rule as _random_rule, random_word as _random_word
 
-W = b"p@ssW0rd"
+W =b"p@ssW0rd"
 KAT = [
     (b"l", b"p@ssw0rd"), (b"u", b"P@SSW0RD"), (b"c", b"P@ssw0rd"), (b"C", b"p@SSW0RD"), (b"t", b"P@SSw0RD"),
     (b"T3", b"p@sSW0rd"), (b"r", b"dr0Wss@p"), (b"d", b"p@ssW0rdp@ssW0rd"), (b"p2", W * 3),
@@ -45,28 +47,6 @@ def test_known_answers(rule, want):
 def test_known_answers_title_case(rule, word, want):
     assert ro.apply_rule(rule, word) == want
     assert _lib_apply(rule, word) == want
-
-
-def _random_rule(rng, fns):
-    """A grammar-generated rule line of the given functions, with random spacing."""
-    out = b""
-    for f in fns:
-        ps = b""
-        for k in ro.KINDS[f]:
-            if k in "NM":
-                # mostly small positions, some up to 'Z' (35)
-                v = int(rng.integers(0, 12)) if rng.random() < 0.8 else int(rng.integers(0, 36))
-                ps += bytes([0x30 + v if v < 10 else 0x41 + v - 10])
-            else:
-                ps += bytes([int(rng.choice(list(b"aeiostAEZ 0159!-@\x00\xff\xe9")))])
-        out += f.encode() + ps + (b" " if rng.random() < 0.3 else b"")
-    return out
-
-
-def _random_word(rng, n):
-    # letters of both cases, digits, separators, high and zero bytes
-    alpha = list(b"abcxyzABCXYZ019 -@!") + [0, 0x7f, 0x80, 0xe9, 0xff, 0x5b, 0x60, 0x7b, 0x40]
-    return bytes(rng.choice(alpha, size=n).astype(np.uint8)) if n else b""
 
 
 def test_interpreter_agrees_with_the_python_statement():
