@@ -31,7 +31,7 @@ EXPORTS = (
     "a5x_memcpy_d2h", "a5x_synchronize", "a5x_debug_stamps", "a5x_debug_plan_word", "a5x_debug_plan_sizes",
     "a5x_debug_piece_build", "a5x_debug_cut_once", "a5x_debug_cplx_build", "a5x_debug_keyspace_cplx_lean",
     "a5x_debug_keyspace_refit", "a5x_debug_keyspace_small_stage", "a5x_debug_keyspace_stage",
-    "a5x_debug_keyspace_large_stage",
+    "a5x_debug_keyspace_large_stage", "a5x_debug_word_flags",
     "a5x_set_targets", "a5x_expand_digest", "a5x_expand_digest_device", "a5x_expand_digest_range_device",
     "a5x_digest_lines_device", "a5x_digest_size", "a5x_hit_digest", "a5x_debug_digest",
     "a5x_format_plain", "a5x_format_hits", "a5x_locate_device", "a5x_split_device",
@@ -135,6 +135,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         L.a5x_debug_keyspace_small_stage.argtypes = [vp, ctypes.POINTER(u32)]
         L.a5x_debug_keyspace_stage.argtypes = [vp, ctypes.POINTER(u32)]
         L.a5x_debug_keyspace_large_stage.argtypes = [vp, i]
+    if hasattr(L, "a5x_debug_word_flags"):
+        L.a5x_debug_word_flags.argtypes = [vp, vp, u64]
     L.a5x_set_targets.argtypes = [vp, i, vp, u64]
     L.a5x_expand_digest.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Stats)]
     L.a5x_expand_digest_device.argtypes = [vp, vp, vp, u64, i, i, i, u64, vp, u64, ctypes.POINTER(u64),

@@ -228,6 +228,7 @@ struct a5x_ctx {
   uint8_t* gscr = nullptr;  // pass G scratch: A5X_G_SLOTS x a5x_gslot_bytes(), allocated on first use
   DevBuf<uint64_t> rec;  // FAST plan records (keyspace tiles of FW_TILE_REC u64)
   bool ks_large_only = false;  // a5x_debug_keyspace_large_stage: the small word stage is not offered
+  uint64_t flags_nw = 0;       // words whose flags the last keyspace pass wrote (a5x_debug_word_flags)
   uint32_t* d_scalars = nullptr;  // S_ALLOC words, indexed by Slot
   uint32_t* h_scalars = nullptr;  // pinned, its host image
   uint64_t* h_totals = nullptr;   // pinned, T_ALLOC u64 indexed by Total
@@ -625,6 +626,7 @@ int run_keyspace(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff, uin
       (rc = grow(c, c->slow_list, nw + 1)) || (rc = grow(c, c->big_list, nw + 1)) || (rc = grow(c, c->glob, nw + 1)) ||
       (rc = grow(c, c->rec, ((nw + FW_TILE - 1) / FW_TILE) * (uint64_t)FW_TILE_REC + ccap * FW_RMAX + 2)))
     return rc;
+  c->flags_nw = nw;
   if (!d_cand_off) {
     if ((rc = grow(c, c->cand_off, nw + 1))) return rc;
     d_cand_off = c->cand_off.p;
@@ -895,6 +897,7 @@ int run_keyspace_mode(a5x_ctx* c, const uint8_t* d_words, const uint64_t* d_woff
       (rc = grow(c, c->glob, nw + 1)) || (rc = grow(c, c->scan_tmp, a5x_scan_tmp_elems(nw + 1) + 16)))
     return rc;
   c->m_nglob = 0;
+  c->flags_nw = nw;
   if (!d_cand_off) {
     if ((rc = grow(c, c->cand_off, nw + 1))) return rc;
     d_cand_off = c->cand_off.p;
@@ -2572,6 +2575,7 @@ int a5x_stream_reserve(a5x_ctx* c, uint64_t words, uint64_t word_bytes) {
   int rc;
   if ((rc = stream_buffers(c, stream_cap()))) return rc;
   // the per-batch keyspace state of a batch of this size, and the staged words
+  c->flags_nw = 0;  // (growing the flags array need not keep the last pass's)
   if ((rc = grow(c, c->s_words, word_bytes + 16)) || (rc = grow(c, c->s_woff, words + 1)) ||
       (rc = grow(c, c->count, words + 1)) || (rc = grow(c, c->bytes, words + 1)) ||
       (rc = grow(c, c->flags, words + 1)) || (rc = grow(c, c->defer, words + 1)) ||
@@ -2705,6 +2709,18 @@ int a5x_debug_keyspace_stage(a5x_ctx* c, uint32_t* out) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out, c->d_scalars + S_STAGE, 4, hipMemcpyDeviceToHost));
+  return A5X_OK;
+}
+
+int a5x_debug_word_flags(a5x_ctx* c, uint32_t* out, uint64_t n) {
+  if (c && c->device < 0) return fail(c, A5X_E_HIP, "host-only context (device -1) cannot run kernels");
+  if (!c || (!out && n)) return A5X_E_ARG;
+  if (n > c->flags_nw)
+    return fail(c, A5X_E_ARG, "flags of %llu words asked, the last keyspace pass had %llu", (unsigned long long)n,
+                (unsigned long long)c->flags_nw);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n) HIPCHK(c, hipMemcpy(out, c->flags.p, n * 4, hipMemcpyDeviceToHost));
   return A5X_OK;
 }
 

@@ -1898,6 +1898,16 @@ struct WordInfo {
   u32 why;         // diagnostics when !fits: 1 long, 2 matches, 3 columns, 4 DP size
 };
 
+// sums and products of the event DP that stop at 2^64 - 1 (wave_setup)
+__device__ __forceinline__ u64 add_sat(u64 a, u64 b) {
+  const u64 r = a + b;
+  return r < a ? ~0ull : r;
+}
+__device__ __forceinline__ u64 mul_sat(u64 a, u64 b) {
+  u64 r;
+  return __builtin_mul_overflow(a, b, &r) ? ~0ull : r;
+}
+
 __device__ __forceinline__ u32 fastdiv(u32 n, u32 magic, u32 shift) {
   u32 q = __umulhi(n, magic);
   return (q + ((n - q) >> 1)) >> shift;
@@ -2073,8 +2083,13 @@ __device__ WordInfo wave_setup(WaveLds<LMAX, MLMAX, DPENT>& S, const Tab& T, con
   I.Cc = C;
   I.W = C + 1;
   if (I.W > 64 || (u64)(m + 1) * I.W > (u64)DPENT) { I.fits = 0; I.why = I.W > 64 ? 3 : 4; return I; }
+  // The tables also hold states no candidate reaches (c substitutions made before event
+  // e < c); their entries pass 64 bits long before the word's own keyspace does (the one
+  // candidate of 63 matches in the window (63, 63) has C(63, 31) of them).  So the sums
+  // saturate at 2^64 - 1 instead of raising the overflow: every term is >= 0, a saturated
+  // entry stays saturated in whatever it is added to, and an entry a candidate reaches is
+  // at most G[0] / H[0] -- the word overflows exactly when those two saturate.
   const u32 W = I.W, c = lane;
-  bool ovf = false;
   for (int e = (int)m; e >= 0; --e) {
     if (c < W) {
       u64 g, h;
@@ -2084,7 +2099,7 @@ __device__ WordInfo wave_setup(WaveLds<LMAX, MLMAX, DPENT>& S, const Tab& T, con
       } else {
         const u32 q = S.evpos[e], qn = S.evpos[e + 1];
         g = S.dp.G[(e + 1) * W + c];
-        h = add_ovf(S.dp.H[(e + 1) * W + c], mul_ovf(g, qn - q, ovf), ovf);
+        h = add_sat(S.dp.H[(e + 1) * W + c], mul_sat(g, qn - q));
         const u32 em = S.evm[e], ms = em >> 8, mc = em & 255u;
         const u32 nc = I.freew ? 1u : c + 1u;
         if (nc <= C) {
@@ -2093,9 +2108,9 @@ __device__ WordInfo wave_setup(WaveLds<LMAX, MLMAX, DPENT>& S, const Tab& T, con
             const u32 p2 = q + key.klen, e2 = S.evidx[p2], lit = S.evpos[e2] - p2;
             const u64 gs = S.dp.G[e2 * W + nc];
             const u64 hs = S.dp.H[e2 * W + nc];
-            g = add_ovf(g, mul_ovf(gs, key.nvals, ovf), ovf);
+            g = add_sat(g, mul_sat(gs, key.nvals));
             const u64 per = (u64)key.sumlen + (u64)key.nvals * lit;
-            h = add_ovf(h, add_ovf(mul_ovf(hs, key.nvals, ovf), mul_ovf(gs, per, ovf), ovf), ovf);
+            h = add_sat(h, add_sat(mul_sat(hs, key.nvals), mul_sat(gs, per)));
           }
         }
       }
@@ -2104,11 +2119,9 @@ __device__ WordInfo wave_setup(WaveLds<LMAX, MLMAX, DPENT>& S, const Tab& T, con
     }
     ws_sync<LMAX>();
   }
-  I.ovf = wave_or_u32(ovf) != 0;
   I.count = S.dp.G[0];
-  bool o2 = false;
-  I.bytes = add_ovf(S.dp.H[0], mul_ovf(S.dp.G[0], S.evpos[0], o2), o2);  // + literal prefix
-  if (o2) I.ovf = 1;
+  I.bytes = add_sat(S.dp.H[0], mul_sat(S.dp.G[0], S.evpos[0]));  // + literal prefix
+  I.ovf = (I.count == ~0ull || I.bytes == ~0ull) ? 1u : 0u;
   return I;
 }
 

@@ -638,6 +638,14 @@ class Context:
         (``a5x_debug_keyspace_large_stage``; tests and A/B runs)."""
         self._chk(self._L.a5x_debug_keyspace_large_stage(self.h, 1 if on else 0))
 
+    def word_flags(self, n: int) -> np.ndarray:
+        """The per-word class flags (``A5X_WF_*``) the last keyspace pass left on the device, for
+        its first ``n`` words; after a refused batch the refused words carry their ``ERR`` bits
+        (``a5x_debug_word_flags``; a test hook)."""
+        out = np.zeros(max(1, n), dtype=np.uint32)
+        self._chk(self._L.a5x_debug_word_flags(self.h, out.ctypes.data, n))
+        return out[:n]
+
     def locate_device(self, d_words: int, d_offs: int, n_words: int, cands, mode: int = MODE_DEFAULT, mn: int = 0,
                       mx: int = 15, stream: int = 0) -> np.ndarray:
         """Output byte offsets of global candidate indices (``a5x_locate_device``)."""

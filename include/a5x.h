@@ -560,6 +560,19 @@ A5X_API int a5x_debug_keyspace_small_stage(a5x_ctx* ctx, uint32_t* out);
 A5X_API int a5x_debug_keyspace_stage(a5x_ctx* ctx, uint32_t* out);
 A5X_API int a5x_debug_keyspace_large_stage(a5x_ctx* ctx, int on);
 
+/* Test hook (GPU test suite): the per-word class flags (A5X_WF_* of csrc/a5x_format.h) that the
+ * context's last keyspace pass left on the device, out[0, n), n at most the words of that pass
+ * (A5X_E_ARG beyond, and before any pass).  A pass that refused the batch (A5X_E_UNSUPPORTED,
+ * A5X_E_OVERFLOW) leaves its flags too: the refused words carry A5X_WF_ERR_BIG (with the reason
+ * in bits 16..23 and the count columns in 24..31) or A5X_WF_ERR_OVF, the others of the batch
+ * whatever the passes that ran before the refusal decided.  After a -r / -s / -s -r pass the
+ * flags are those engines': A5X_WF_FAST (with A5X_WF_VIRT / A5X_WF_VFIX and the FAST fields) for
+ * a word on the FAST path, A5X_WF_GLOB for a word of mode pass G, A5X_WF_ERR_BIG / A5X_WF_ERR_OVF
+ * for one refused by the count pass (a candidate too long is found by the length pass and leaves
+ * no bit), 0 otherwise; the class bits RADIX / BIN / GENERAL / BIG / DEFER mean nothing
+ * there.  Synchronises the device.  Never called by a compute path. */
+A5X_API int a5x_debug_word_flags(a5x_ctx* ctx, uint32_t* out, uint64_t n);
+
 /* Test hook (CPU test suite): the digest of msg[0, len) computed on the host by the
  * __host__ __device__ core the digest kernels run (a5x_sha.h: SHA-1 and the SHA-2 family;
  * a5x_nest.h: the nested algorithms 16..22), a5x_digest_size(algo) bytes into out.

@@ -239,10 +239,24 @@ def test_virtual_fixed_width_long_words(tmp_path, mode, mn):
         words.append(w.encode())
     words += [("xyzxyzx" * 9)[:n].encode() + b"aa" for n in range(5, 62, 7)]
     words += ["αxxxxxxβxxxxxxαxxxxxxβ".encode(), "γγγγ".encode(), ("aseot" * 12).encode()]
+    fixed = [b"sxyzaa", b"aaxs", b"xsxaxxa"]  # a tied pattern beside a lone unit: sub-word 0 has candidates
+    words += fixed
     want = _oracle(str(p), words, mode, mn, 15)
+    VFIX = (1 << 5) | (1 << 7) | (1 << 29)  # A5X_WF_FAST | A5X_WF_VIRT | A5X_WF_VFIX
     with Context(0) as c:
         c.load_tables([str(p)])
         cnt, byt = c.keyspace(*pack_words(words), mode, mn, 15)
+        # the descriptor path ran: these words are not left to the planner (a5x_debug_word_flags)
+        # (asserted on words chosen for it, not on the random ones or the xyz...aa family: a word
+        # gets a descriptor only when it is virtual at all -- at most four tied patterns, 16
+        # occurrences -- and its all-keep sub-word has candidates, which with min >= 1 takes a
+        # lone unit beside the tied pattern; the others may rightly be the planner's)
+        fl = c.word_flags(len(words))
+        for w, f in zip(words[-len(fixed):], fl[-len(fixed):]):
+            assert int(f) & VFIX == VFIX, (mode, mn, w, hex(int(f)))
+        if mn == 0:  # (with min >= 1 their all-keep sub-word is empty: no descriptor)
+            for i in (-len(fixed) - 3, -len(fixed) - 2):
+                assert int(fl[i]) & VFIX == VFIX, (mode, words[i].decode(), hex(int(fl[i])))
         got = c.expand_words(words, mode, mn, 15)
         small = []
         for i in range(0, len(words), 16):
